@@ -1,6 +1,7 @@
 """Headline benchmark: agent-steps/s of the batched colony (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c3|c2|c5|kremling]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one Delta t = 1 s of the whole colony: every agent's kinetics
 (adaptive DP5(4), FP64, rtol 1e-8 / atol 1e-12), the local-environment
@@ -9,6 +10,20 @@ exchange scatter.  Default workload = BASELINE config 4 (1M agents on a
 4096 x 4096 lattice, glucose + acetate), strong-scaled over N ranks by row
 bands (one process per GPU, RCCL halo exchange).  Inputs are resident in
 HBM before the timed region.  Rank 0 prints one JSON line.
+
+A plain run does what the headline figure needs and no more: set up, warm up,
+time the K steps, write the outputs (--dump-outputs), print the line.  With
+--full it also measures, after the timed region and outside it, everything
+else the line can carry: the kinetics / diffusion split, the fused pass and
+the copy floor (roofline), the exact-mode pass, the CPU baselines, and (C4 on
+one GPU) the bounded C5 and Kremling legs (secondary).
+
+--dump-outputs DIR writes what the last timed step left a caller of
+Colony.step -- agent state, fluxes, exchange counts, the lattice planes -- as
+DIR/<name>.npy (float64; a fixed seeded sample of the columns of an array
+over its share of DUMP_BYTES).  The inputs are seeded, and the colony is put
+back to its state after the W warmup steps before the timed region, so the
+files of two runs with the same arguments compare value for value.
 
 Untimed before the K timed steps: W warmup steps, then settle steps until
 the warmup has lasted --settle-ms.  The chip runs the first ~10 ms after an
@@ -128,6 +143,7 @@ KREMLING_RHS_FLOPS = 71
 N_SIMDS = 256 * 4          # MI355X: 256 CUs x 4 SIMDs (MI355X_MICROARCH.md)
 KREMLING_NY = 15
 SPLIT_STEPS = 6            # eager steps timed for the kinetics / diffusion split (the first is dropped)
+DUMP_BYTES = 48 * 1024 * 1024      # --dump-outputs: all files of one run together
 
 
 def stencil_kernel_name(variant, depth, mode='exact', pass_bytes=None):
@@ -202,9 +218,16 @@ def parse(argv=None):
                    help='after the W warmup steps, run more untimed steps until the warmup has kept the GPU '
                         'busy this long (power-management transient, profiles/r02g_eager_trace_gaps.log); '
                         'reported as untimed_settle_steps')
-    p.add_argument('--no-cpu-baseline', action='store_true')
+    p.add_argument('--full', action='store_true',
+                   help='after the timed steps, also measure what the headline does not need: the kinetics / '
+                        'diffusion split, the pass and copy-floor roofline, the exact-mode pass, the CPU '
+                        'baselines and (C4 on one GPU) the C5 and Kremling legs')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='write what the last timed step computed to DIR/<name>.npy (float64, at most DUMP_BYTES '
+                        'in all: a fixed seeded sample of the larger arrays)')
+    p.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baselines')
     p.add_argument('--secondary-steps', type=int, default=10,
-                   help='C4 on one GPU: timed steps of the bounded C5 and Kremling legs (0 = skip them)')
+                   help='--full, C4 on one GPU: timed steps of the bounded C5 and Kremling legs (0 = skip them)')
     p.add_argument('--cpu-seconds', type=float, default=12.0)
     args = p.parse_args(argv)
     if args.steps is None:
@@ -262,6 +285,37 @@ def settle_steps_needed(warmup_s: float, warmup_steps: int, settle_ms: float, ca
         return 0
     per = max(warmup_s / warmup_steps, 1e-6)
     return int(min(cap, np.ceil(max(0.0, settle_ms * 1e-3 - warmup_s) / per)))
+
+
+def dump_arrays(path, arrays, rank=0, world=1, budget=None):
+    """Write each (name, tensor [..., n]) of `arrays` as path/<name>.npy in float64.
+    The files share `budget` bytes (DUMP_BYTES) equally; an array over its share
+    keeps a sample of its last axis (flattened planes: of their cells), drawn by a
+    generator seeded with configs.SEED: the same columns in every run.  Ranks of
+    a multi-GPU run write <name>.rank<r>.npy."""
+    os.makedirs(path, exist_ok=True)
+    share = (DUMP_BYTES if budget is None else budget) // max(1, len(arrays))
+    for name, t in arrays:
+        t = t.reshape(-1, t.shape[-1])
+        rows, n = t.shape
+        keep = max(1, share // (8 * rows))
+        if keep < n:
+            idx = np.sort(np.random.default_rng(configs.SEED).choice(n, keep, replace=False))
+            t = t[:, torch.from_numpy(idx).to(t.device)]
+        if world > 1:
+            name = '%s.rank%d' % (name, rank)
+        np.save(os.path.join(path, name + '.npy'), t.to(torch.float64).cpu().numpy())
+
+
+def colony_outputs(col, lat):
+    """What a caller of Colony.step holds after a step: the agents' state, fluxes
+    and exchange counts (and cell rows), and this rank's rows of every plane."""
+    out = [('conc', col.conc[:, :col.n]), ('flux', col.flux[:, :col.n]), ('counts', col.counts[:, :col.n])]
+    if col.cells is not None:
+        out.append(('cell', col.cell[:, :col.n]))
+    if lat is not None:
+        out += [('field_' + mol, lat.owned(mol).reshape(1, -1)) for mol in lat.molecules]
+    return out
 
 
 def build_rank(args, rank, world, dev):
@@ -519,6 +573,9 @@ def run_kremling(args, rank, world, dev, dist):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     col.check_status()
+    if args.dump_outputs:
+        dump_arrays(args.dump_outputs, [('state', col.state), ('flux', col.flux), ('counts', col.counts)],
+                    rank, world)
     el = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     agents = torch.tensor([float(n_local * args.steps)], dtype=torch.float64, device=dev)
     if dist is not None:
@@ -548,7 +605,7 @@ def run_kremling(args, rank, world, dev, dist):
                      'flops_per_attempt': flops_attempt,
                      'hbm_gbps': n_local * bytes_agent / (kms * 1e-3) / 1e9},
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         cores = int(os.environ.get('OMP_NUM_THREADS', '0') or 0) or len(os.sched_getaffinity(0))
         jobs = [('kremling', (states[:, a].tolist() + [0.0] * 4, float(vols[a]))) for a in range(0, n_local, n_local // 256)]
         out['cpu_baseline'] = cpu_baseline_odeint(jobs, args.cpu_seconds, cores)
@@ -574,7 +631,7 @@ def main():
         out = run_kremling(args, rank, world, dev, dist)
     else:
         out = run(args, rank, world, dev, dist)
-    if out is not None and world == 1 and args.workload == 'c4' and args.secondary_steps > 0:
+    if out is not None and world == 1 and args.full and args.workload == 'c4' and args.secondary_steps > 0:
         # the north star's FP64 bar is carried by C5 and Kremling: bounded legs of both,
         # after the headline and outside its timed region, in the same JSON line
         out['secondary'] = secondary_legs(args, dev)
@@ -654,6 +711,17 @@ def run(args, rank, world, dev, dist):
     for k in range(args.warmup):
         one_step(mk() if lat is None else None)
     barrier()
+    # The settle steps and replays below are counted by the clock, so they leave the
+    # colony a different number of steps on in every run.  The state after the W
+    # warmup steps is kept here and put back before the timed region: the K timed
+    # steps, and what --dump-outputs writes of the last, start from the same state
+    # in every run.  (A dividing colony re-lays its agents out and cannot be put
+    # back: its files repeat only where untimed_settle_steps is 0, as with the 1M
+    # agents of C5, whose warmup steps outlast --settle-ms.)
+    kept = None
+    if not divides and args.settle_ms > 0:
+        kept = [(t, t.clone()) for t in (col.conc, col.h_state) + ((lat.fields,) if lat is not None else ())]
+        kept_clock = (col.time, col.step_index)
     # Settle: the chip runs the first ~10 ms of load after an idle spell up to
     # 40 % slower (profiles/r02g_eager_trace_gaps.log), and W short steps (a
     # 0.3-ms banded step at 8 GPUs) do not cover that.  More untimed steps run
@@ -714,6 +782,11 @@ def run(args, rank, world, dev, dist):
             settle_steps += (1 + int(need.item())) * per_graph
         graph_info = {'steps_per_graph': per_graph, 'replays': args.steps // per_graph,
                       'untimed_warmup_replay_steps': per_graph, 'steps_per_launch': spl}
+    if kept is not None:
+        for t, t_kept in kept:
+            t.copy_(t_kept)
+        col.time, col.step_index = kept_clock
+        del kept
     agent_steps = 0          # agents integrated, summed over the timed steps (divisions grow n)
     n_start = col.n
     if divides:
@@ -746,13 +819,16 @@ def run(args, rank, world, dev, dist):
     barrier()
     elapsed = time.perf_counter() - t0
     col.check_status()
-    stencil_pass_ms = time_stencil_pass(lat, args.stencil_depth) if lat is not None else None
+    if args.dump_outputs:
+        dump_arrays(args.dump_outputs, colony_outputs(col, lat), rank, world)
+    full = args.full
+    stencil_pass_ms = time_stencil_pass(lat, args.stencil_depth) if lat is not None and full else None
     exact_pass_ms = None
-    if lat is not None and args.stencil_mode != 'exact':
+    if lat is not None and full and args.stencil_mode != 'exact':
         stencil_mode('exact')             # the bit-exact pass on the same planes, for comparison
         exact_pass_ms = time_stencil_pass(lat, args.stencil_depth)
         stencil_mode(args.stencil_mode)
-    copy_floor = time_copy_floor(lat) if lat is not None and world == 1 else None
+    copy_floor = time_copy_floor(lat) if lat is not None and full and world == 1 else None
     el = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     n_agents = torch.tensor([float(agent_steps)], dtype=torch.float64, device=dev)
     per_step = None
@@ -770,6 +846,8 @@ def run(args, rank, world, dev, dist):
     elif lat is None:
         kin_ms = sum(t['kin'][0].elapsed_time(t['kin'][1]) for t in timing) / args.steps
         diff_ms = None
+    elif not full:
+        kin_ms = diff_ms = None       # a lattice step's split takes steps of its own (below)
     elif use_graph and not banded:
         # The kinetics / diffusion split from graph-replayed steps: a replay of the
         # timed steps' graph with device timestamps (vk_timestamp, one-lane kernels)
@@ -862,7 +940,7 @@ def run(args, rank, world, dev, dist):
                           'roofline_bound': 'fp64' if t_flop >= t_byte else 'hbm',
                           'roofline_frac': max(t_flop, t_byte) / (kin_ms * 1e-3)})
         roofline = None
-        if lat is not None:
+        if lat is not None and full:
             # dominant kernel: one fused pass of `depth` substeps (k_diffuse_wt<depth>)
             depth = args.stencil_depth
             cells = (lat.row_hi - lat.row_lo) * lat.ny * len(lat.molecules)
@@ -911,7 +989,7 @@ def run(args, rank, world, dev, dist):
                 floor_ms = cms * bytes_per_launch / cbytes
                 roofline['copy_floor'] = {'copy_ms': cms, 'copy_gbps': cbytes / (cms * 1e-3) / 1e9,
                                           'floor_ms_per_launch': floor_ms, 'frac': floor_ms / launch_ms}
-        else:
+        elif lat is None:
             roofline = {'bound': 'fp64-valu', 'kernel': kname_i,
                         'achieved': integ.get('achieved_tflops'), 'peak': FP64_PEAK_TFLOPS,
                         'unit': 'TFLOP/s', 'frac': integ.get('frac'), 'traffic': None}
@@ -935,7 +1013,7 @@ def run(args, rank, world, dev, dist):
             'integrator': integ,
             'hip_graph': graph_info,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and full and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(args, col, host_state)
             # leg (ii): the reference's own odeint on the restated RHS, sampled agents
             params, conc, _ = host_state
@@ -962,7 +1040,7 @@ def secondary_legs(args, dev):
         sub = argparse.Namespace(**vars(args))
         sub.workload, sub.steps, sub.warmup, sub.no_cpu_baseline = wl, args.secondary_steps, 3, True
         sub.stencil_mode, sub.stencil_depth, sub.stencil_kernel, sub.stencil_rows = 'fma', None, None, None
-        sub.agents, sub.couple, sub.graph = None, False, 'auto'
+        sub.agents, sub.couple, sub.graph, sub.dump_outputs = None, False, 'auto', None
         try:
             o = run_kremling(sub, 0, 1, dev, None) if wl == 'kremling' else run(sub, 0, 1, dev, None)
         except Exception as e:          # a failed leg must not cost the headline its line

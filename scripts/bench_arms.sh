@@ -10,7 +10,7 @@ IFS='|' read -ra A <<< "$ARMS"
 for r in $(seq 1 ${ROUNDS:-3}); do
   for arm in "${A[@]}"; do
     lab=${arm%%:*}; args=${arm#*:}
-    timeout -k 10 200 python bench.py --no-cpu-baseline --secondary-steps 0 --steps 20 $args > $O/${lab}_$r.json 2> $O/${lab}_$r.err \
+    timeout -k 10 200 python bench.py --full --no-cpu-baseline --secondary-steps 0 --steps 20 $args > $O/${lab}_$r.json 2> $O/${lab}_$r.err \
       || { echo "arm $lab failed"; tail -5 $O/${lab}_$r.err; exit 2; }
     python -c "import json; d=json.loads(open('$O/${lab}_$r.json').read().strip().splitlines()[-1]); print('$lab round $r: %.4f ms/step  pass %.1f us frac %.3f' % (d['ms_per_step'], d['roofline']['avg_launch_ms']*1e3, d['roofline']['frac']))"
   done

@@ -10,7 +10,7 @@ tail -2 $O/pytest.log
 for r in 1 2; do
   for arm in new old; do
     if [ $arm = old ]; then export VK_DOPRI5_WAVE_TEMPLATE=$PWD/scripts/ab/wave_spec_old.hip.in; else unset VK_DOPRI5_WAVE_TEMPLATE; fi
-    timeout -k 10 300 python bench.py --workload c5 --no-cpu-baseline --steps ${STEPS:-10} > $O/c5_${arm}_$r.log 2>&1 || { tail -20 $O/c5_${arm}_$r.log; exit 2; }
+    timeout -k 10 300 python bench.py --full --workload c5 --no-cpu-baseline --steps ${STEPS:-10} > $O/c5_${arm}_$r.log 2>&1 || { tail -20 $O/c5_${arm}_$r.log; exit 2; }
     tail -1 $O/c5_${arm}_$r.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); i=d.get('integrator') or {}; print('$arm', '$r', '%.4e' % d['value'], '%.3f ms' % d['ms_per_step'], 'fp64', i.get('frac'), 'kin_ms', i.get('ms_per_step', i.get('kernel_ms')))"
   done
 done

@@ -29,19 +29,19 @@ for st in "$@"; do
         || { tail -20 $O/smoke.log; exit 2; }
       tail -1 $O/smoke.log ;;
     bench)
-      timeout -k 10 400 python bench.py > $O/bench_c4.log 2>&1 || { tail -20 $O/bench_c4.log; exit 3; }
+      timeout -k 10 400 python bench.py --full > $O/bench_c4.log 2>&1 || { tail -20 $O/bench_c4.log; exit 3; }
       tail -1 $O/bench_c4.log | cut -c1-400 ;;
     gloo2)
-      timeout -k 10 300 python bench.py --gpus 2 --dist-backend gloo --steps 3 --warmup 1 --no-cpu-baseline \
+      timeout -k 10 300 python bench.py --full --gpus 2 --dist-backend gloo --steps 3 --warmup 1 --no-cpu-baseline \
         > $O/bench_gloo2.log 2>&1 || { tail -30 $O/bench_gloo2.log; exit 4; }
       tail -1 $O/bench_gloo2.log | cut -c1-300 ;;
     gloo4)
-      timeout -k 10 300 python bench.py --gpus 4 --dist-backend gloo --steps 3 --warmup 1 --no-cpu-baseline \
+      timeout -k 10 300 python bench.py --full --gpus 4 --dist-backend gloo --steps 3 --warmup 1 --no-cpu-baseline \
         > $O/bench_gloo4.log 2>&1 || { tail -30 $O/bench_gloo4.log; exit 4; }
       tail -1 $O/bench_gloo4.log | cut -c1-300 ;;
     prof)
       timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- \
-        python3 bench.py --no-cpu-baseline > $O/bench_c4_rocprof.log 2>&1 || { tail -20 $O/bench_c4_rocprof.log; exit 5; }
+        python3 bench.py --full --no-cpu-baseline > $O/bench_c4_rocprof.log 2>&1 || { tail -20 $O/bench_c4_rocprof.log; exit 5; }
       tail -1 $O/bench_c4_rocprof.log | cut -c1-300 ;;
     pmc)
       i=0

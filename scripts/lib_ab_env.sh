@@ -9,7 +9,7 @@ tail -1 $O/pytest.log
 for r in 1 2 3; do
   for arm in head new; do
     if [ $arm = head ]; then export VK_KINETICS_LIB=$PWD/${OLD_LIB:-lens_amd/lib/ab/libvk_kinetics_head.so}; else unset VK_KINETICS_LIB; fi
-    timeout -k 10 200 python bench.py --no-cpu-baseline --secondary-steps 0 --steps 20 > $O/${arm}_$r.json 2> $O/${arm}_$r.err || { echo "arm $arm failed"; tail -5 $O/${arm}_$r.err; exit 2; }
+    timeout -k 10 200 python bench.py --full --no-cpu-baseline --secondary-steps 0 --steps 20 > $O/${arm}_$r.json 2> $O/${arm}_$r.err || { echo "arm $arm failed"; tail -5 $O/${arm}_$r.err; exit 2; }
     python -c "import json; d=json.loads(open('$O/${arm}_$r.json').read().strip().splitlines()[-1]); print('$arm round $r: %.4f ms/step  pass %.1f us frac %.3f' % (d['ms_per_step'], d['roofline']['avg_launch_ms']*1e3, d['roofline']['frac']))"
   done
 done

@@ -9,7 +9,7 @@ for r in 1 2 3; do
     cp lens_amd/lib/ab_$arm.so lens_amd/lib/libvk_kinetics.so
     line="$arm round $r:"
     for w in c2 c3; do
-      timeout -k 10 200 python bench.py --workload $w --no-cpu-baseline > $O/${w}_${arm}_$r.json 2> $O/${w}_${arm}_$r.err \
+      timeout -k 10 200 python bench.py --full --workload $w --no-cpu-baseline > $O/${w}_${arm}_$r.json 2> $O/${w}_${arm}_$r.err \
         || { echo "arm $arm $w failed"; tail -5 $O/${w}_${arm}_$r.err; exit 1; }
       line="$line $w $(python -c "import json; d=json.loads(open('$O/${w}_${arm}_$r.json').read().strip().splitlines()[-1]); print('%.3e (%.5f ms)' % (d['value'], d['ms_per_step']))")"
     done

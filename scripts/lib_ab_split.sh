@@ -8,7 +8,7 @@ O=gpurun_out/${TAG:-libabsplit}; mkdir -p $O
 for r in 1 2; do
   for arm in ${ARMS:-base new}; do
     cp lens_amd/lib/ab_$arm.so lens_amd/lib/libvk_kinetics.so
-    timeout -k 10 200 python bench.py --workload c3 --no-cpu-baseline --steps 40 > $O/c3_${arm}_$r.json 2> $O/c3_${arm}_$r.err \
+    timeout -k 10 200 python bench.py --full --workload c3 --no-cpu-baseline --steps 40 > $O/c3_${arm}_$r.json 2> $O/c3_${arm}_$r.err \
       || { echo "arm $arm failed"; tail -5 $O/c3_${arm}_$r.err; exit 1; }
     c3=$(python -c "import json; d=json.loads(open('$O/c3_${arm}_$r.json').read().strip().splitlines()[-1]); print('%.4f' % d['ms_per_step'])")
     for w in 8 4; do

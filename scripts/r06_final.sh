@@ -28,7 +28,7 @@ if [ "${PMC:-1}" = 1 ]; then
 fi
 if [ "${WORKLOADS_RUN:-1}" = 1 ]; then
   TAG=$T bash scripts/bench_workloads.sh || exit 8
-  timeout -k 10 400 python bench.py --stencil-mode exact --no-cpu-baseline --secondary-steps 0 > $O/bench_c4_exact.log 2>&1 || { tail -20 $O/bench_c4_exact.log; exit 9; }
+  timeout -k 10 400 python bench.py --full --stencil-mode exact --no-cpu-baseline --secondary-steps 0 > $O/bench_c4_exact.log 2>&1 || { tail -20 $O/bench_c4_exact.log; exit 9; }
   tail -1 $O/bench_c4_exact.log | cut -c1-200
 fi
 if [ "${GLOO:-1}" = 1 ]; then

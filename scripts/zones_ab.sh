@@ -37,7 +37,7 @@ ARMS="z0:"
 for z in "${ZS[@]}"; do ARMS="$ARMS|z$z:"; done
 for r in 1 2; do
   for z in 0,0 "${ZS[@]}"; do
-    VK_ZONES=$z timeout -k 10 200 python bench.py --no-cpu-baseline --secondary-steps 0 --steps 20 > $O/b_${z}_$r.json 2> $O/b_${z}_$r.err || { echo "arm $z failed"; tail -5 $O/b_${z}_$r.err; exit 3; }
+    VK_ZONES=$z timeout -k 10 200 python bench.py --full --no-cpu-baseline --secondary-steps 0 --steps 20 > $O/b_${z}_$r.json 2> $O/b_${z}_$r.err || { echo "arm $z failed"; tail -5 $O/b_${z}_$r.err; exit 3; }
     python -c "import json; d=json.loads(open('$O/b_${z}_$r.json').read().strip().splitlines()[-1]); print('zones $z round $r: %.4f ms/step  pass %.1f us frac %.3f' % (d['ms_per_step'], d['roofline']['avg_launch_ms']*1e3, d['roofline']['frac']))"
   done
 done

@@ -145,3 +145,71 @@ def test_pass_plan_restates_the_library_planner():
         d = min(9 if depth == 10 else depth | 1, 15)
         assert sum(ks) == n_sub and all(k % 2 == 1 and k <= d for k in ks), (n_sub, depth, ks)
         assert len(ks) % 2 == n_sub % 2
+
+
+def test_plain_run_is_the_default_and_full_is_an_option():
+    """--full and --dump-outputs exist and are off by default; the options of the
+    measurements behind --full still parse."""
+    args = bench.parse([])
+    assert args.full is False and args.dump_outputs is None
+    args = bench.parse(['--full', '--dump-outputs', 'out', '--no-cpu-baseline', '--secondary-steps', '0'])
+    assert args.full is True and args.dump_outputs == 'out'
+    assert bench.parse(['--steps', '7']).steps == 7
+
+
+def test_extra_measurements_run_only_behind_full():
+    """Every call of a measurement that takes a run of its own (the pass and copy-floor
+    timing, the CPU baselines, the secondary legs) sits under a test of --full."""
+    import ast
+    tree = ast.parse(open(os.path.join(bench.REPO, 'bench.py')).read())
+    extra = {'time_stencil_pass', 'time_copy_floor', 'cpu_baseline', 'cpu_baseline_odeint', 'secondary_legs'}
+
+    def tests_full(node):
+        return any((isinstance(n, ast.Name) and n.id == 'full') or (isinstance(n, ast.Attribute) and n.attr == 'full')
+                   for n in ast.walk(node))
+
+    def visit(node, guarded, inside):
+        for child in ast.iter_child_nodes(node):
+            g = guarded or (isinstance(node, (ast.If, ast.IfExp)) and child is not node.test and tests_full(node.test))
+            if isinstance(child, ast.FunctionDef):
+                visit(child, False, child.name)
+                continue
+            if isinstance(child, ast.Call) and isinstance(child.func, ast.Name) and child.func.id in extra:
+                seen.add(child.func.id)
+                # the exact-mode pass is timed inside time-the-pass's own guarded block
+                assert g or inside in extra, (child.func.id, child.lineno)
+            visit(child, g, inside)
+
+    seen = set()
+    visit(tree, False, None)
+    assert seen == extra
+
+
+def test_dump_arrays_writes_a_fixed_sample_within_the_budget(tmp_path):
+    """Arrays within their share are written whole, larger ones as the same seeded
+    sample of columns in every call, all float64 and together within the budget."""
+    import numpy as np
+    import torch
+    small = torch.arange(12, dtype=torch.float64).reshape(3, 4)
+    big = torch.arange(5 * 1000, dtype=torch.float64).reshape(5, 1000)
+    ints = torch.arange(2 * 1000, dtype=torch.int64).reshape(2, 1000)
+    plane = torch.arange(7 * 300, dtype=torch.float64).reshape(1, -1)
+    arrays = [('small', small), ('big', big), ('ints', ints), ('plane', plane)]
+    budget = 4 * 8 * 500
+    out = []
+    for d in ('a', 'b'):
+        bench.dump_arrays(str(tmp_path / d), arrays, budget=budget)
+        assert sorted(os.listdir(tmp_path / d)) == ['big.npy', 'ints.npy', 'plane.npy', 'small.npy']
+        out.append({n: np.load(tmp_path / d / (n + '.npy')) for n, _ in arrays})
+    a, b = out
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= budget
+    assert all(np.array_equal(a[n], b[n]) for n in a)
+    assert np.array_equal(a['small'], small.numpy())
+    assert a['big'].shape == (5, 100) and a['ints'].shape == (2, 250) and a['plane'].shape == (1, 500)
+    # a sample is whole columns of the array, in their order
+    cols = a['big'][0].astype(int)
+    assert np.all(np.diff(cols) > 0) and np.array_equal(a['big'], big.numpy()[:, cols])
+    assert np.array_equal(a['ints'][1], a['ints'][0] + 1000)
+    bench.dump_arrays(str(tmp_path / 'r'), [('small', small)], rank=1, world=2)
+    assert os.listdir(tmp_path / 'r') == ['small.rank1.npy']
