@@ -21,6 +21,16 @@ TEMPLATE = os.environ.get('VK_DOPRI5_TEMPLATE') or os.path.join(os.path.dirname(
                                                                  'vk_dopri5_spec.hip.in')
 
 
+DP45_HEADER = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc', 'vk_dp45.h')
+
+
+def _dp45_core() -> str:
+    """Text of the DP45 core header for a template's ``@@DP45@@`` slot, read anew for every
+    source (hiprtc sees no include path: the header all compiled kernels include is pasted in)."""
+    with open(DP45_HEADER) as f:
+        return f.read()
+
+
 def _f(x: float) -> str:
     return repr(float(x))
 
@@ -88,6 +98,7 @@ def dopri5_source(t: RateLawTable) -> str:
         '#define NY %d' % max(t.n_dyn + t.n_reactions, 1),
     ])
     return (src.replace('@@DEFS@@', defs)
+               .replace('@@DP45@@', _dp45_core())
                .replace('@@RHS@@', rhs_body(t))
                .replace('@@COUNTS@@', counts_body(t))
                .replace('@@INVKM@@', invkm_body(t)))
@@ -292,4 +303,5 @@ def wave_source(t: RateLawTable, wpe: int = 3, pad_writes: int = 0, lds_ops: int
                       % (e % W, '\n'.join(terms), e))
     with open(WAVE_TEMPLATE) as f:
         src = f.read()
-    return src.replace('@@DEFS@@', defs).replace('@@TABLES@@', tables).replace('@@COUNTS@@', '\n'.join(counts))
+    return (src.replace('@@DEFS@@', defs).replace('@@DP45@@', _dp45_core()).replace('@@TABLES@@', tables)
+               .replace('@@COUNTS@@', '\n'.join(counts)))

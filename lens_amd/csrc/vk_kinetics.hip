@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "vk_internal.h"
+#include "vk_dp45.h"
 
 namespace vk {
 
@@ -285,15 +286,6 @@ __device__ __forceinline__ void fluxes_exact(const vk_dev_table &t, const double
     }
 }
 
-// Python int(x) truncates toward zero; out-of-range / non-finite -> flagged.
-__device__ __forceinline__ int64_t trunc_count(double x, int32_t &st) {
-    if (!(fabs(x) < 9.2e18)) {
-        st |= VK_AGENT_NONFINITE;
-        return 0;
-    }
-    return (int64_t)x;
-}
-
 __global__ __launch_bounds__(256) void k_rate_fluxes(vk_dev_table t, int64_t n, int64_t ld,
                                                      const double *__restrict__ params,
                                                      const double *__restrict__ conc,
@@ -339,7 +331,7 @@ __global__ __launch_bounds__(256) void k_step_euler(vk_dev_table t, int64_t n, i
         const int j0 = TI(t, ex_ptr, e), j1 = TI(t, ex_ptr, e + 1);
         for (int j = j0; j < j1; ++j) {
             const double sf = (TD(t, ex_coeff, j) * flux[(int64_t)TI(t, ex_rxn, j) * ld + a]) * dt;
-            c += trunc_count(sf * mc, st);
+            c += dp45::trunc_count(sf * mc, st);
         }
         counts[(int64_t)e * ld + a] = c;
     }
@@ -395,57 +387,9 @@ extern "C" int vk_step_euler(const vk_table *t, int64_t n, int64_t ld, double dt
 // entries, a compile-time constant so the seven stage vectors live in VGPRs.
 // LDS tile (BS lanes): rows [0,n_species) species, then n_reactions flux
 // rows, then n_params parameter rows holding kcat or 1/Km (0 for a falsy Km).
-
-namespace dp {
-constexpr double a21 = 1.0 / 5.0;
-constexpr double a31 = 3.0 / 40.0, a32 = 9.0 / 40.0;
-constexpr double a41 = 44.0 / 45.0, a42 = -56.0 / 15.0, a43 = 32.0 / 9.0;
-constexpr double a51 = 19372.0 / 6561.0, a52 = -25360.0 / 2187.0, a53 = 64448.0 / 6561.0,
-                 a54 = -212.0 / 729.0;
-constexpr double a61 = 9017.0 / 3168.0, a62 = -355.0 / 33.0, a63 = 46732.0 / 5247.0,
-                 a64 = 49.0 / 176.0, a65 = -5103.0 / 18656.0;
-constexpr double b1 = 35.0 / 384.0, b3 = 500.0 / 1113.0, b4 = 125.0 / 192.0,
-                 b5 = -2187.0 / 6784.0, b6 = 11.0 / 84.0;
-// e = b - bhat (4th-order embedded), scipy RK45's E up to sign
-constexpr double e1 = 71.0 / 57600.0, e3 = -71.0 / 16695.0, e4 = 71.0 / 1920.0,
-                 e5 = -17253.0 / 339200.0, e6 = 22.0 / 525.0, e7 = -1.0 / 40.0;
-constexpr double SAFETY = 0.9, MIN_FACTOR = 0.2, MAX_FACTOR = 10.0;
-
-// The adaptive kernels are tolerance-parity (within 1e-6 of odeint, SURVEY
-// 8a), not bit-parity, so they use the cheap forms of their two costliest
-// operations; the specialised kernel (vk_dopri5_spec.hip.in) uses the same
-// two, so it stays bit-identical to the table walk.
-// a/b by the hardware reciprocal plus one Newton step (~1e-15 relative, as
-// vk_kremling.hip's; a second step bought nothing the 1e-6 odeint bar sees;
-// a zero divisor gives NaN instead of inf -- flagged non-finite either way).
-__device__ __forceinline__ double fdiv(double a, double b) {
-    double r = __builtin_amdgcn_rcp(b);
-    r = fma(fma(-b, r, 1.0), r, r);
-    return a * r;
-}
-
-// en^-0.2 for the step-size factor (scipy RK45's error_norm ** (-1/5)) without
-// libm's exp2 / log2: a single-precision estimate from the hardware v_log_f32 /
-// v_exp_f32 (~1e-6 relative), then two Newton steps on en * y^5 = 1 in double
-// (quadratic: ~1e-11, then rounding).  en is clamped to [1e-30, 1e30] so the
-// float stays normal; outside that range the factor is capped anyway (at 10
-// for en < 1e-30, at 0.2 for en > 1e30, callers' fmin / fmax).  The same code in
-// every DP45 kernel (vk_kinetics.hip, the specialised templates, vk_kremling.hip)
-// keeps them bit-identical to one another.  exp2(log2()) kept its polynomial
-// constants in VGPRs across the attempt loop: the C5 wavefront kernel spilled
-// them and reloaded eight in series per attempt (round 6).
-__device__ __forceinline__ double step_pow(double en) {
-    const double e = fmin(fmax(en, 1e-30), 1e30);
-    double y = (double)__builtin_amdgcn_exp2f(-0.2f * __builtin_amdgcn_logf((float)e));
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-        const double y2 = y * y;
-        const double r = fma(-e, y2 * y2 * y, 1.0);   // 1 - e y^5
-        y = fma(0.2 * y, r, y);
-    }
-    return y;
-}
-}  // namespace dp
+// The tableau, the cheap division, the stage combinations, the step controller,
+// the initial-step rule and the wavefront reduction come from vk_dp45.h, the
+// core every DP45 kernel shares.
 
 constexpr int DP_BS = 256;
 
@@ -471,7 +415,7 @@ __device__ __forceinline__ double rate_law_tile(const vk_dev_table &t, int l, co
             term *= fma(cl[TI(t, mem_species, m) * DP_BS + lane], pl[TI(t, mem_param, m) * DP_BS + lane], 1.0);
         den += term - 1.0;
     }
-    return dp::fdiv(num, den);
+    return dp45::vk_div(num, den);
 }
 
 template <int NY>
@@ -568,9 +512,7 @@ __global__ __launch_bounds__(DP_BS) void k_dopri5_thread(vk_dev_table t, int64_t
 #pragma unroll
         for (int i = 0; i < NY; ++i) k2[i] = k2[i] - k1[i];
         const double d2 = rms_norm<NY>(k2, sc, ny) / h0;
-        const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3)
-                                                        : pow(0.01 / fmax(d1, d2), 0.2);
-        h = fmin(fmin(100.0 * h0, h1), dt);
+        h = fmin(dp45::initial_step(h0, dp45::initial_h1(d1, d2, h0, 1.0)), dt);
     }
 
     double tt = 0.0;
@@ -585,43 +527,36 @@ __global__ __launch_bounds__(DP_BS) void k_dopri5_thread(vk_dev_table t, int64_t
         if (tt + hs >= dt) { hs = dt - tt; last = true; }
         ++ns;
 #pragma unroll
-        for (int i = 0; i < NY; ++i) yt[i] = fma(hs, dp::a21 * k1[i], y[i]);
+        for (int i = 0; i < NY; ++i) yt[i] = dp45::stage2(hs, y[i], k1[i]);
         rhs_tile<NY>(t, yt, k2, cl, fl, pl, lane);
 #pragma unroll
-        for (int i = 0; i < NY; ++i) yt[i] = fma(hs, fma(dp::a32, k2[i], dp::a31 * k1[i]), y[i]);
+        for (int i = 0; i < NY; ++i) yt[i] = dp45::stage3(hs, y[i], k1[i], k2[i]);
         rhs_tile<NY>(t, yt, k3, cl, fl, pl, lane);
 #pragma unroll
-        for (int i = 0; i < NY; ++i)
-            yt[i] = fma(hs, fma(dp::a43, k3[i], fma(dp::a42, k2[i], dp::a41 * k1[i])), y[i]);
+        for (int i = 0; i < NY; ++i) yt[i] = dp45::stage4(hs, y[i], k1[i], k2[i], k3[i]);
         rhs_tile<NY>(t, yt, k4, cl, fl, pl, lane);
 #pragma unroll
-        for (int i = 0; i < NY; ++i)
-            yt[i] = fma(hs, fma(dp::a54, k4[i], fma(dp::a53, k3[i], fma(dp::a52, k2[i], dp::a51 * k1[i]))), y[i]);
+        for (int i = 0; i < NY; ++i) yt[i] = dp45::stage5(hs, y[i], k1[i], k2[i], k3[i], k4[i]);
         rhs_tile<NY>(t, yt, k5, cl, fl, pl, lane);
 #pragma unroll
-        for (int i = 0; i < NY; ++i)
-            yt[i] = fma(hs, fma(dp::a65, k5[i], fma(dp::a64, k4[i], fma(dp::a63, k3[i],
-                        fma(dp::a62, k2[i], dp::a61 * k1[i])))), y[i]);
+        for (int i = 0; i < NY; ++i) yt[i] = dp45::stage6(hs, y[i], k1[i], k2[i], k3[i], k4[i], k5[i]);
         rhs_tile<NY>(t, yt, k6, cl, fl, pl, lane);
 #pragma unroll
-        for (int i = 0; i < NY; ++i)
-            yt[i] = fma(hs, fma(dp::b6, k6[i], fma(dp::b5, k5[i], fma(dp::b4, k4[i],
-                        fma(dp::b3, k3[i], dp::b1 * k1[i])))), y[i]);
+        for (int i = 0; i < NY; ++i) yt[i] = dp45::stage7(hs, y[i], k1[i], k3[i], k4[i], k5[i], k6[i]);
         rhs_tile<NY>(t, yt, k7, cl, fl, pl, lane);
         double en = 0.0;
 #pragma unroll
         for (int i = 0; i < NY; ++i) {
             if (i < ny) {
-                const double err = hs * fma(dp::e7, k7[i], fma(dp::e6, k6[i], fma(dp::e5, k5[i],
-                                       fma(dp::e4, k4[i], fma(dp::e3, k3[i], dp::e1 * k1[i])))));
-                const double q = dp::fdiv(err, fma(fmax(fabs(y[i]), fabs(yt[i])), rtol, atol));
+                const double err = dp45::err_term(hs, k1[i], k3[i], k4[i], k5[i], k6[i], k7[i]);
+                const double q = dp45::err_ratio(err, y[i], yt[i], rtol, atol);
                 en = fma(q, q, en);
             }
         }
         en = sqrt(en / ny);
         if (!isfinite(en)) { st |= VK_AGENT_NONFINITE; break; }
         if (en < 1.0) {
-            double factor = (en == 0.0) ? dp::MAX_FACTOR : fmin(dp::MAX_FACTOR, dp::SAFETY * dp::step_pow(en));
+            double factor = dp45::accept_factor(en);
             if (rejected) factor = fmin(1.0, factor);
             tt = last ? dt : tt + hs;
 #pragma unroll
@@ -630,7 +565,7 @@ __global__ __launch_bounds__(DP_BS) void k_dopri5_thread(vk_dev_table t, int64_t
             h = hs * factor;
             rejected = false;
         } else {
-            h = hs * fmax(dp::MIN_FACTOR, dp::SAFETY * dp::step_pow(en));
+            h = hs * dp45::reject_factor(en);
             rejected = true;
         }
     }
@@ -655,7 +590,7 @@ __global__ __launch_bounds__(DP_BS) void k_dopri5_thread(vk_dev_table t, int64_t
         int64_t c = 0;
         const int j0 = TI(t, ex_ptr, e), j1 = TI(t, ex_ptr, e + 1);
         for (int j = j0; j < j1; ++j)
-            c += trunc_count((TD(t, ex_coeff, j) * fl[TI(t, ex_rxn, j) * DP_BS + lane]) * mc, st);
+            c += dp45::trunc_count((TD(t, ex_coeff, j) * fl[TI(t, ex_rxn, j) * DP_BS + lane]) * mc, st);
         counts[(int64_t)e * ld + a] = c;
     }
     if (h_state) h_state[a] = h_keep;
@@ -683,60 +618,6 @@ __global__ __launch_bounds__(DP_BS) void k_dopri5_thread(vk_dev_table t, int64_t
 constexpr int DW = 64;
 constexpr int DW_WAVES = 4;   // agents (waves) per workgroup
 
-// LDS communication between the lanes of ONE wave: a wave's LDS operations
-// execute in order, so only the compiler must be kept from reordering.
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Wavefront sum, identical in every lane: a butterfly from the smallest
-// distance up.  Distances 1 and 2 are quad_perm DPP moves; once quads (then
-// 8-lane groups) hold equal values, row_half_mirror / row_mirror pair them
-// exactly as distances 4 / 8 would; distances 16 and 32 use the gfx950 row
-// swaps (v_permlane16/32_swap), after which each lane holds v[l] and
-// v[l ^ d] and adds them (FP addition commutes, so every lane gets the same
-// bits).  No LDS round trip, unlike __shfl_xor (ds_bpermute).
-__device__ __forceinline__ double dpp_pair(double v, int ctrl) {
-    int2 x = __builtin_bit_cast(int2, v);
-    int2 y;
-    switch (ctrl) {   // the DPP control must be a compile-time constant
-        case 0xB1:
-            y.x = __builtin_amdgcn_mov_dpp(x.x, 0xB1, 0xf, 0xf, false);
-            y.y = __builtin_amdgcn_mov_dpp(x.y, 0xB1, 0xf, 0xf, false);
-            break;
-        case 0x4E:
-            y.x = __builtin_amdgcn_mov_dpp(x.x, 0x4E, 0xf, 0xf, false);
-            y.y = __builtin_amdgcn_mov_dpp(x.y, 0x4E, 0xf, 0xf, false);
-            break;
-        case 0x141:
-            y.x = __builtin_amdgcn_mov_dpp(x.x, 0x141, 0xf, 0xf, false);
-            y.y = __builtin_amdgcn_mov_dpp(x.y, 0x141, 0xf, 0xf, false);
-            break;
-        default:
-            y.x = __builtin_amdgcn_mov_dpp(x.x, 0x140, 0xf, 0xf, false);
-            y.y = __builtin_amdgcn_mov_dpp(x.y, 0x140, 0xf, 0xf, false);
-            break;
-    }
-    return v + __builtin_bit_cast(double, y);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-    v = dpp_pair(v, 0xB1);    // quad_perm [1,0,3,2]: lane ^ 1
-    v = dpp_pair(v, 0x4E);    // quad_perm [2,3,0,1]: lane ^ 2
-    v = dpp_pair(v, 0x141);   // row_half_mirror: the other quad of the 8-lane group
-    v = dpp_pair(v, 0x140);   // row_mirror: the other 8-lane group of the row
-    int2 x = __builtin_bit_cast(int2, v);
-    auto lo = __builtin_amdgcn_permlane16_swap(x.x, x.x, false, false);
-    auto hi = __builtin_amdgcn_permlane16_swap(x.y, x.y, false, false);
-    v = __builtin_bit_cast(double, make_int2(lo[0], hi[0])) + __builtin_bit_cast(double, make_int2(lo[1], hi[1]));
-    x = __builtin_bit_cast(int2, v);
-    lo = __builtin_amdgcn_permlane32_swap(x.x, x.x, false, false);
-    hi = __builtin_amdgcn_permlane32_swap(x.y, x.y, false, false);
-    return __builtin_bit_cast(double, make_int2(lo[0], hi[0])) + __builtin_bit_cast(double, make_int2(lo[1], hi[1]));
-}
-
 // rate law l from the agent's LDS tile (cl: species, pl: kcat or 1/Km);
 // table indices are lane-divergent here, so they are plain (vector) loads
 __device__ __forceinline__ double rate_law_wave(const vk_dev_table &t, const int32_t *ib, int l, const double *cl,
@@ -759,7 +640,7 @@ __device__ __forceinline__ double rate_law_wave(const vk_dev_table &t, const int
         for (int m = m0; m < m1; ++m) term *= fma(cl[ib[t.o_mem_species + m]], pl[ib[t.o_mem_param + m]], 1.0);
         den += term - 1.0;
     }
-    return dp::fdiv(num, den);
+    return dp45::vk_div(num, den);
 }
 
 template <int NSLOT>
@@ -772,15 +653,15 @@ __device__ __forceinline__ void rhs_wave(const vk_dev_table &t, const int32_t *i
         const int i = lane + DW * k;
         if (i < nd) cl[i] = y[k];
     }
-    wave_sync();
+    dp45::wave_sync();
     for (int l = lane; l < nl; l += DW) rl[l] = rate_law_wave(t, ib, l, cl, pl);
-    wave_sync();
+    dp45::wave_sync();
     for (int r = lane; r < nr; r += DW) {
         double f = 0.0;
         for (int k = ib[t.o_rx_ptr + r]; k < ib[t.o_rx_ptr + r + 1]; ++k) f += rl[ib[t.o_rx_rl + k]];
         fl[r] = f;
     }
-    wave_sync();
+    dp45::wave_sync();
 #pragma unroll
     for (int k = 0; k < NSLOT; ++k) {
         const int i = lane + DW * k;
@@ -793,7 +674,7 @@ __device__ __forceinline__ void rhs_wave(const vk_dev_table &t, const int32_t *i
         }
         dy[k] = d;
     }
-    wave_sync();   // the next RHS overwrites cl / fl
+    dp45::wave_sync();   // the next RHS overwrites cl / fl
 }
 
 template <int NSLOT>
@@ -806,7 +687,7 @@ __device__ __forceinline__ double wave_rms(const double (&v)[NSLOT], const doubl
             s = fma(q, q, s);
         }
     }
-    return sqrt(wave_sum(s) / ny);
+    return sqrt(dp45::wave_sum(s) / ny);
 }
 
 template <int NSLOT>
@@ -841,14 +722,14 @@ __global__ __launch_bounds__(DW * DW_WAVES) void k_dopri5_wave(vk_dev_table t, i
 
     for (int s = lane; s < ns_; s += DW) cl[s] = conc[(int64_t)s * ld + a];
     for (int p = lane; p < np_; p += DW) pl[p] = params[(int64_t)p * ld + a];
-    wave_sync();
+    dp45::wave_sync();
     const int n_mem = ib[t.o_set_ptr + ib[t.o_rl_den_ptr + t.n_rate_laws]];
     for (int m = lane; m < n_mem; m += DW) {
         const int p = ib[t.o_mem_param + m];
         const double km = params[(int64_t)p * ld + a];
         pl[p] = (km != 0.0) ? 1.0 / km : 0.0;
     }
-    wave_sync();
+    dp45::wave_sync();
 
     double y[NSLOT], k1[NSLOT], k2[NSLOT], k3[NSLOT], k4[NSLOT], k5[NSLOT], k6[NSLOT], k7[NSLOT], yt[NSLOT];
 #pragma unroll
@@ -872,8 +753,7 @@ __global__ __launch_bounds__(DW * DW_WAVES) void k_dopri5_wave(vk_dev_table t, i
 #pragma unroll
         for (int k = 0; k < NSLOT; ++k) k2[k] = k2[k] - k1[k];
         const double d2 = wave_rms<NSLOT>(k2, sc, lane, ny) / h0;
-        const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : pow(0.01 / fmax(d1, d2), 0.2);
-        h = fmin(fmin(100.0 * h0, h1), dt);
+        h = fmin(dp45::initial_step(h0, dp45::initial_h1(d1, d2, h0, 1.0)), dt);
     }
 
     double tt = 0.0, h_keep = h;
@@ -887,43 +767,36 @@ __global__ __launch_bounds__(DW * DW_WAVES) void k_dopri5_wave(vk_dev_table t, i
         if (tt + hs >= dt) { hs = dt - tt; last = true; }
         ++nsteps;
 #pragma unroll
-        for (int k = 0; k < NSLOT; ++k) yt[k] = fma(hs, dp::a21 * k1[k], y[k]);
+        for (int k = 0; k < NSLOT; ++k) yt[k] = dp45::stage2(hs, y[k], k1[k]);
         rhs_wave<NSLOT>(t, ib, db, yt, k2, cl, fl, pl, rl, lane);
 #pragma unroll
-        for (int k = 0; k < NSLOT; ++k) yt[k] = fma(hs, fma(dp::a32, k2[k], dp::a31 * k1[k]), y[k]);
+        for (int k = 0; k < NSLOT; ++k) yt[k] = dp45::stage3(hs, y[k], k1[k], k2[k]);
         rhs_wave<NSLOT>(t, ib, db, yt, k3, cl, fl, pl, rl, lane);
 #pragma unroll
-        for (int k = 0; k < NSLOT; ++k)
-            yt[k] = fma(hs, fma(dp::a43, k3[k], fma(dp::a42, k2[k], dp::a41 * k1[k])), y[k]);
+        for (int k = 0; k < NSLOT; ++k) yt[k] = dp45::stage4(hs, y[k], k1[k], k2[k], k3[k]);
         rhs_wave<NSLOT>(t, ib, db, yt, k4, cl, fl, pl, rl, lane);
 #pragma unroll
-        for (int k = 0; k < NSLOT; ++k)
-            yt[k] = fma(hs, fma(dp::a54, k4[k], fma(dp::a53, k3[k], fma(dp::a52, k2[k], dp::a51 * k1[k]))), y[k]);
+        for (int k = 0; k < NSLOT; ++k) yt[k] = dp45::stage5(hs, y[k], k1[k], k2[k], k3[k], k4[k]);
         rhs_wave<NSLOT>(t, ib, db, yt, k5, cl, fl, pl, rl, lane);
 #pragma unroll
-        for (int k = 0; k < NSLOT; ++k)
-            yt[k] = fma(hs, fma(dp::a65, k5[k], fma(dp::a64, k4[k], fma(dp::a63, k3[k],
-                        fma(dp::a62, k2[k], dp::a61 * k1[k])))), y[k]);
+        for (int k = 0; k < NSLOT; ++k) yt[k] = dp45::stage6(hs, y[k], k1[k], k2[k], k3[k], k4[k], k5[k]);
         rhs_wave<NSLOT>(t, ib, db, yt, k6, cl, fl, pl, rl, lane);
 #pragma unroll
-        for (int k = 0; k < NSLOT; ++k)
-            yt[k] = fma(hs, fma(dp::b6, k6[k], fma(dp::b5, k5[k], fma(dp::b4, k4[k],
-                        fma(dp::b3, k3[k], dp::b1 * k1[k])))), y[k]);
+        for (int k = 0; k < NSLOT; ++k) yt[k] = dp45::stage7(hs, y[k], k1[k], k3[k], k4[k], k5[k], k6[k]);
         rhs_wave<NSLOT>(t, ib, db, yt, k7, cl, fl, pl, rl, lane);
         double e2 = 0.0;
 #pragma unroll
         for (int k = 0; k < NSLOT; ++k) {
             if (lane + DW * k < ny) {
-                const double err = hs * fma(dp::e7, k7[k], fma(dp::e6, k6[k], fma(dp::e5, k5[k],
-                                       fma(dp::e4, k4[k], fma(dp::e3, k3[k], dp::e1 * k1[k])))));
-                const double q = dp::fdiv(err, fma(fmax(fabs(y[k]), fabs(yt[k])), rtol, atol));
+                const double err = dp45::err_term(hs, k1[k], k3[k], k4[k], k5[k], k6[k], k7[k]);
+                const double q = dp45::err_ratio(err, y[k], yt[k], rtol, atol);
                 e2 = fma(q, q, e2);
             }
         }
-        const double en = sqrt(wave_sum(e2) / ny);
+        const double en = sqrt(dp45::wave_sum(e2) / ny);
         if (!isfinite(en)) { st |= VK_AGENT_NONFINITE; break; }
         if (en < 1.0) {
-            double factor = (en == 0.0) ? dp::MAX_FACTOR : fmin(dp::MAX_FACTOR, dp::SAFETY * dp::step_pow(en));
+            double factor = dp45::accept_factor(en);
             if (rejected) factor = fmin(1.0, factor);
             tt = last ? dt : tt + hs;
 #pragma unroll
@@ -932,7 +805,7 @@ __global__ __launch_bounds__(DW * DW_WAVES) void k_dopri5_wave(vk_dev_table t, i
             h = hs * factor;
             rejected = false;
         } else {
-            h = hs * fmax(dp::MIN_FACTOR, dp::SAFETY * dp::step_pow(en));
+            h = hs * dp45::reject_factor(en);
             rejected = true;
         }
     }
@@ -954,14 +827,14 @@ __global__ __launch_bounds__(DW * DW_WAVES) void k_dopri5_wave(vk_dev_table t, i
             flux[(int64_t)(i - nd) * ld + a] = y[k] / dt;
         }
     }
-    wave_sync();
+    dp45::wave_sync();
     if (__any(bad)) st |= VK_AGENT_NONFINITE;
     const double mc = m2c[a];
     int32_t cst = 0;
     for (int e = lane; e < t.n_ext; e += DW) {
         int64_t c = 0;
         for (int j = ib[t.o_ex_ptr + e]; j < ib[t.o_ex_ptr + e + 1]; ++j)
-            c += trunc_count((db[t.o_ex_coeff + j] * fl[ib[t.o_ex_rxn + j]]) * mc, cst);
+            c += dp45::trunc_count((db[t.o_ex_coeff + j] * fl[ib[t.o_ex_rxn + j]]) * mc, cst);
         counts[(int64_t)e * ld + a] = c;
     }
     if (__any(cst != 0)) st |= VK_AGENT_NONFINITE;

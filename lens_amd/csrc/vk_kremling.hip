@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "vk_internal.h"
+#include "vk_dp45.h"
 
 namespace {
 
@@ -47,14 +48,7 @@ struct Kp {  // device copy of vk_kremling_params plus host-derived constants
     int n_int, m_int; // the exponents n, m when they are small non-negative integers, else -1
 };
 
-// division with the hardware reciprocal refined by one Newton step (~1e-15
-// relative; tolerance parity against odeint, like every adaptive kernel here: a
-// second step cost 6 % of the Kremling step, profiles/r06/r06t/)
-__device__ __forceinline__ double kdiv(double a, double b) {
-    double r = __builtin_amdgcn_rcp(b);
-    r = fma(fma(-b, r, 1.0), r, r);
-    return a * r;
-}
+using dp45::vk_div;   // the DP45 kernels' cheap division (tolerance parity against odeint)
 
 // x**e for the model's exponents: repeated products for a small integer e
 // (the reference's defaults n = 2, m = 1), pow otherwise.  EI >= 0: the exponent
@@ -89,24 +83,24 @@ __device__ __forceinline__ void kremling_rhs(const Kp &p, const double (&s)[KS],
     double uptake1, transporter1;
     if (g6p) {
         transporter1 = UHPT;
-        uptake1 = kdiv(p.kg6p * (transporter1 * G6P_e), p.Kg6p + G6P_e);
+        uptake1 = vk_div(p.kg6p * (transporter1 * G6P_e), p.Kg6p + G6P_e);
     } else {
         transporter1 = LACZ;
-        uptake1 = kdiv(p.klac * (transporter1 * LCTS_e),
-                       p.Km_lac + LCTS_e * (1.0 + kdiv(kdiv(p.x0 - XP, p.x0), p.Kieiia)));
+        uptake1 = vk_div(p.klac * (transporter1 * LCTS_e),
+                         p.Km_lac + LCTS_e * (1.0 + vk_div(vk_div(p.x0 - XP, p.x0), p.Kieiia)));
     }
-    const double uptake2 = kdiv(p.kptsup * XP * (PTSG * GLC_e),
-                                p.KglcKx0 + GLC_e * p.Keiiap * p.x0 + XP * p.Kglc + XP * GLC_e);
+    const double uptake2 = vk_div(p.kptsup * XP * (PTSG * GLC_e),
+                                  p.KglcKx0 + GLC_e * p.Keiiap * p.x0 + XP * p.Kglc + XP * GLC_e);
     const double xp2 = XP * XP;
     const double xp6 = xp2 * xp2 * xp2;
-    const double hill = p.kb + kdiv(p.ksyn * xp6, xp6 + p.K6);
+    const double hill = p.kb + vk_div(p.ksyn * xp6, xp6 + p.K6);
     double synthesis1, synthesis2;
     if (g6p) {
-        synthesis1 = kdiv(p.k1 * hill * uptake1, p.K1 + uptake1);
-        synthesis2 = kdiv(p.k2 * kdiv(p.KI, transporter1 + p.KI) * hill * uptake2, p.K2 + uptake2);
+        synthesis1 = vk_div(p.k1 * hill * uptake1, p.K1 + uptake1);
+        synthesis2 = vk_div(p.k2 * vk_div(p.KI, transporter1 + p.KI) * hill * uptake2, p.K2 + uptake2);
     } else {
-        synthesis1 = kdiv(p.k3 * hill * uptake1, p.K3 + uptake1);
-        synthesis2 = kdiv(p.k2 * hill * uptake2, p.K2 + uptake2);
+        synthesis1 = vk_div(p.k3 * hill * uptake1, p.K3 + uptake1);
+        synthesis2 = vk_div(p.k2 * hill * uptake2, p.K2 + uptake2);
     }
     const double rgly = p.kgly * G6P;
     const double rpdh = p.kpdh * PYR;
@@ -129,41 +123,6 @@ __device__ __forceinline__ void kremling_rhs(const Kp &p, const double (&s)[KS],
     da[1] = rpyk;      // PYK
     da[2] = d[9];      // glc__D_e
 }
-
-// en^-0.2 for the step-size factor (scipy RK45's error_norm ** (-1/5)) without
-// libm's exp2 / log2: a single-precision estimate from the hardware v_log_f32 /
-// v_exp_f32 (~1e-6 relative), then two Newton steps on en * y^5 = 1 in double
-// (quadratic: ~1e-11, then rounding).  en is clamped to [1e-30, 1e30] so the
-// float stays normal; outside that range the factor is capped anyway (at 10
-// for en < 1e-30, at 0.2 for en > 1e30, callers' fmin / fmax).  The same code in
-// every DP45 kernel (vk_kinetics.hip, the specialised templates, vk_kremling.hip)
-// keeps them bit-identical to one another.  exp2(log2()) kept its polynomial
-// constants in VGPRs across the attempt loop: the C5 wavefront kernel spilled
-// them and reloaded eight in series per attempt (round 6).
-__device__ __forceinline__ double step_factor(double en) {
-    const double e = fmin(fmax(en, 1e-30), 1e30);
-    double y = (double)__builtin_amdgcn_exp2f(-0.2f * __builtin_amdgcn_logf((float)e));
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-        const double y2 = y * y;
-        const double r = fma(-e, y2 * y2 * y, 1.0);   // 1 - e y^5
-        y = fma(0.2 * y, r, y);
-    }
-    return y;
-}
-
-namespace dpk {
-constexpr double a21 = 1.0 / 5.0;
-constexpr double a31 = 3.0 / 40.0, a32 = 9.0 / 40.0;
-constexpr double a41 = 44.0 / 45.0, a42 = -56.0 / 15.0, a43 = 32.0 / 9.0;
-constexpr double a51 = 19372.0 / 6561.0, a52 = -25360.0 / 2187.0, a53 = 64448.0 / 6561.0, a54 = -212.0 / 729.0;
-constexpr double a61 = 9017.0 / 3168.0, a62 = -355.0 / 33.0, a63 = 46732.0 / 5247.0, a64 = 49.0 / 176.0,
-                 a65 = -5103.0 / 18656.0;
-constexpr double b1 = 35.0 / 384.0, b3 = 500.0 / 1113.0, b4 = 125.0 / 192.0, b5 = -2187.0 / 6784.0,
-                 b6 = 11.0 / 84.0;
-constexpr double e1 = 71.0 / 57600.0, e3 = -71.0 / 16695.0, e4 = 71.0 / 1920.0, e5 = -17253.0 / 339200.0,
-                 e6 = 22.0 / 525.0, e7 = -1.0 / 40.0;
-}  // namespace dpk
 
 // reference component i (0..14) of the error norm: species, then A0, A0 (PPS), A1, A2
 __device__ __forceinline__ int acc_of(int i) { return i == 11 || i == 12 ? 0 : i - 12; }
@@ -223,9 +182,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void k
             d2 = fma(q, q, d2);
         }
         d2 = sqrt(d2 / KNY) / h0;
-        const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6 * grid_h, h0 * 1e-3)
-                                                        : pow(0.01 / fmax(d1, d2), 0.2);
-        h = fmin(100.0 * h0, h1);
+        h = dp45::initial_step(h0, dp45::initial_h1(d1, d2, h0, grid_h));   // no clamp: the grid clips each step
     }
     double acc[4] = {0.0, 0.0, 0.0, 0.0};   // sum over grid points of the flux integrals (t_0 term is 0)
     int ns = 0;
@@ -241,52 +198,45 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void k
             if (tt + hs >= t_end) { hs = t_end - tt; last = true; }
             ++ns;
 #pragma unroll
-            for (int j = 0; j < KA; ++j) { s5[j] = dpk::b1 * k1a[j]; se[j] = dpk::e1 * k1a[j]; }
+            for (int j = 0; j < KA; ++j) { s5[j] = dp45::b1 * k1a[j]; se[j] = dp45::e1 * k1a[j]; }
 #pragma unroll
-            for (int i = 0; i < KS; ++i) yt[i] = fma(hs, dpk::a21 * k1[i], y[i]);
+            for (int i = 0; i < KS; ++i) yt[i] = dp45::stage2(hs, y[i], k1[i]);
             kremling_rhs<NI, MI>(p, yt, k2, ka);                      // b2 = e2 = 0
 #pragma unroll
-            for (int i = 0; i < KS; ++i) yt[i] = fma(hs, fma(dpk::a32, k2[i], dpk::a31 * k1[i]), y[i]);
+            for (int i = 0; i < KS; ++i) yt[i] = dp45::stage3(hs, y[i], k1[i], k2[i]);
             kremling_rhs<NI, MI>(p, yt, k3, ka);
 #pragma unroll
-            for (int j = 0; j < KA; ++j) { s5[j] = fma(dpk::b3, ka[j], s5[j]); se[j] = fma(dpk::e3, ka[j], se[j]); }
+            for (int j = 0; j < KA; ++j) { s5[j] = fma(dp45::b3, ka[j], s5[j]); se[j] = fma(dp45::e3, ka[j], se[j]); }
 #pragma unroll
-            for (int i = 0; i < KS; ++i)
-                yt[i] = fma(hs, fma(dpk::a43, k3[i], fma(dpk::a42, k2[i], dpk::a41 * k1[i])), y[i]);
+            for (int i = 0; i < KS; ++i) yt[i] = dp45::stage4(hs, y[i], k1[i], k2[i], k3[i]);
             kremling_rhs<NI, MI>(p, yt, k4, ka);
 #pragma unroll
-            for (int j = 0; j < KA; ++j) { s5[j] = fma(dpk::b4, ka[j], s5[j]); se[j] = fma(dpk::e4, ka[j], se[j]); }
+            for (int j = 0; j < KA; ++j) { s5[j] = fma(dp45::b4, ka[j], s5[j]); se[j] = fma(dp45::e4, ka[j], se[j]); }
 #pragma unroll
-            for (int i = 0; i < KS; ++i)
-                yt[i] = fma(hs, fma(dpk::a54, k4[i], fma(dpk::a53, k3[i], fma(dpk::a52, k2[i], dpk::a51 * k1[i]))), y[i]);
+            for (int i = 0; i < KS; ++i) yt[i] = dp45::stage5(hs, y[i], k1[i], k2[i], k3[i], k4[i]);
             kremling_rhs<NI, MI>(p, yt, k5, ka);
 #pragma unroll
-            for (int j = 0; j < KA; ++j) { s5[j] = fma(dpk::b5, ka[j], s5[j]); se[j] = fma(dpk::e5, ka[j], se[j]); }
+            for (int j = 0; j < KA; ++j) { s5[j] = fma(dp45::b5, ka[j], s5[j]); se[j] = fma(dp45::e5, ka[j], se[j]); }
 #pragma unroll
-            for (int i = 0; i < KS; ++i)
-                yt[i] = fma(hs, fma(dpk::a65, k5[i], fma(dpk::a64, k4[i], fma(dpk::a63, k3[i],
-                            fma(dpk::a62, k2[i], dpk::a61 * k1[i])))), y[i]);
+            for (int i = 0; i < KS; ++i) yt[i] = dp45::stage6(hs, y[i], k1[i], k2[i], k3[i], k4[i], k5[i]);
             kremling_rhs<NI, MI>(p, yt, k6, ka);
 #pragma unroll
             for (int j = 0; j < KA; ++j) {
-                s5[j] = fma(dpk::b6, ka[j], s5[j]);
-                se[j] = fma(dpk::e6, ka[j], se[j]);
+                s5[j] = fma(dp45::b6, ka[j], s5[j]);
+                se[j] = fma(dp45::e6, ka[j], se[j]);
                 yta[j] = fma(hs, s5[j], ya[j]);
             }
 #pragma unroll
-            for (int i = 0; i < KS; ++i)
-                yt[i] = fma(hs, fma(dpk::b6, k6[i], fma(dpk::b5, k5[i], fma(dpk::b4, k4[i],
-                            fma(dpk::b3, k3[i], dpk::b1 * k1[i])))), y[i]);
+            for (int i = 0; i < KS; ++i) yt[i] = dp45::stage7(hs, y[i], k1[i], k3[i], k4[i], k5[i], k6[i]);
             kremling_rhs<NI, MI>(p, yt, k7, ka);                      // FSAL: k7 is the next step's k1
 #pragma unroll
-            for (int j = 0; j < KA; ++j) se[j] = fma(dpk::e7, ka[j], se[j]);
+            for (int j = 0; j < KA; ++j) se[j] = fma(dp45::e7, ka[j], se[j]);
             double en = 0.0;
 #pragma unroll
             for (int i = 0; i < KNY; ++i) {
                 double err, yo, yn;
                 if (i < KS) {
-                    err = hs * fma(dpk::e7, k7[i], fma(dpk::e6, k6[i], fma(dpk::e5, k5[i],
-                                   fma(dpk::e4, k4[i], fma(dpk::e3, k3[i], dpk::e1 * k1[i])))));
+                    err = dp45::err_term(hs, k1[i], k3[i], k4[i], k5[i], k6[i], k7[i]);
                     yo = y[i];
                     yn = yt[i];
                 } else {
@@ -294,13 +244,13 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void k
                     yo = ya[acc_of(i)];
                     yn = yta[acc_of(i)];
                 }
-                const double q = kdiv(err, fma(fmax(fabs(yo), fabs(yn)), rtol, atol));
+                const double q = dp45::err_ratio(err, yo, yn, rtol, atol);
                 en = fma(q, q, en);
             }
             en = sqrt(en / KNY);
             if (!isfinite(en)) { st |= VK_AGENT_NONFINITE; break; }
             if (en < 1.0) {
-                double factor = (en == 0.0) ? 10.0 : fmin(10.0, 0.9 * step_factor(en));
+                double factor = dp45::accept_factor(en);
                 if (rejected) factor = fmin(1.0, factor);
                 tt = last ? t_end : tt + hs;
 #pragma unroll
@@ -311,7 +261,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void k
                 h = last ? fmax(h, hs * factor) : hs * factor;
                 rejected = false;
             } else {
-                h = hs * fmax(0.2, 0.9 * step_factor(en));
+                h = hs * dp45::reject_factor(en);
                 rejected = true;
             }
         }

@@ -30,6 +30,18 @@ def test_generated_source_compiles_for_gfx950(name, tmp_path):
     _hipcc_compile('#include <hip/hip_runtime.h>\n' + dopri5_source(t), tmp_path)
 
 
+def test_both_templates_carry_the_dp45_header_text():
+    """The hiprtc sources hold csrc/vk_dp45.h verbatim (the header the compiled DP45
+    kernels include), read when the source is generated, and no slot is left unfilled."""
+    from lens_amd import codegen
+    cfg = configs.glc_lct_config()
+    t = compile_rate_laws(cfg['reactions'], cfg['kinetic_parameters'])
+    with open(codegen.DP45_HEADER) as f:
+        core = f.read()
+    for src in (dopri5_source(t), codegen.wave_source(t)):
+        assert src.count(core) == 1 and '@@DP45@@' not in src
+
+
 def _py_rhs(t, conc, params):
     """Evaluate the generated rhs body in Python (same expression text)."""
     p = params.copy()

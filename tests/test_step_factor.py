@@ -1,5 +1,5 @@
-"""The DP45 step factor en^-0.2 as every DP45 kernel computes it (round 6:
-vk_kinetics.hip dp::step_pow, the specialised templates, vk_kremling.hip): a
+"""The DP45 step factor en^-0.2 as every DP45 kernel computes it
+(dp45::step_pow in lens_amd/csrc/vk_dp45.h, the one definition): a
 single-precision estimate from the hardware log2 / exp2 (modelled here as the
 float32 result perturbed by up to +-2.5e-7, more than the instructions'
 error), then two Newton steps on en * y^5 = 1 in double, en clamped to
