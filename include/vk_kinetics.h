@@ -537,6 +537,88 @@ typedef struct vk_expr_table {
 int vk_expression_step(const vk_expr_table *t, int64_t n_agents, int64_t ld, double dt, double *conc,
                        double *update, const double *u, int32_t accumulate, vk_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Motile agents: chemotaxis, and re-binning that stays on the device
+ *
+ *   vk_motility_step
+ *       replaces, per agent and inner update, ReceptorCluster.next_update
+ *       (vivarium/processes/chemoreceptor_cluster.py:166-209: methylation with
+ *       its clamp quirk, piecewise-linear offset energy, MWC free energies,
+ *       P_on) and MotorActivity.next_update (vivarium/processes/
+ *       coarse_motor.py:134-164: CheY-P, motor bias, switching rates, the
+ *       run/tumble switch; thrust and torque as run() / tumble() :177-190 emit
+ *       them).  The reference then moves the cell with pymunk (multibody); the
+ *       move here -- constant run speed, Gaussian heading jitter while
+ *       tumbling, reflecting walls -- is THIS ENGINE'S STAND-IN, not reference
+ *       parity.  The agent's new bin is computed with vk_bin_sites' arithmetic.
+ *   vk_occupancy_sort + vk_exchange_ordered
+ *       replace the host-side occupancy (two sorts, a unique, a host read of
+ *       the occupied-bin count) + vk_exchange_sorted after agents move: the
+ *       same per-bin sums in the same agent order, bit for bit, with no host
+ *       read -- the whole step can be captured into a graph.
+ * ------------------------------------------------------------------------- */
+
+/* Rows of the per-agent motility array motil[VK_MOTIL_ROWS][ld]. */
+enum vk_motil_row {
+    VK_MOTIL_N_METHYL = 0,        /* methyl groups on the receptor cluster (0..8) */
+    VK_MOTIL_ACTIVITY = 1,        /* chemoreceptor_activity, P_on                  */
+    VK_MOTIL_CHEY_P = 2,          /* CheY_P                                        */
+    VK_MOTIL_CCW_MOTOR_BIAS = 3,  /* ccw_motor_bias                                */
+    VK_MOTIL_CCW_TO_CW = 4,       /* ccw_to_cw (1/s)                               */
+    VK_MOTIL_MOTOR_STATE = 5,     /* motor_state: 0 run, 1 tumble                  */
+    VK_MOTIL_ANGLE = 6,           /* heading (rad)                                 */
+    VK_MOTIL_THRUST = 7,          /* pN: 250 running, 100 tumbling                 */
+    VK_MOTIL_TORQUE = 8,          /* heading change / dt while tumbling, else 0    */
+    VK_MOTIL_ROWS = 9
+};
+
+/* The reference defaults of both processes, plus this engine's two kinematic
+ * constants.  CheR / CheB are in mM as the reference holds them; the kernel
+ * uses them in uM as x * 1e3 (the reference converts through pint; that factor
+ * is not pinned here).                                                       */
+typedef struct vk_motility_params {
+    double n_Tar, n_Tsr;                 /* receptors per cluster                     */
+    double K_Tar_off, K_Tar_on;          /* mM                                        */
+    double K_Tsr_off, K_Tsr_on;          /* mM                                        */
+    double k_meth, k_demeth, adapt_rate;
+    double CheR, CheB;                   /* mM                                        */
+    double k_y, k_s, k_z, gamma_Y, adapt_precision;
+    double mb_0, cw_to_ccw, cw_to_ccw_leak;
+    double run_speed;                    /* um/s (engine kinematics)                  */
+    double tumble_sigma;                 /* rad/s heading jitter (engine kinematics)  */
+    uint64_t seed;                       /* Philox key                                */
+} vk_motility_params;
+
+/* `substeps` inner updates of dt / substeps for agents [0, n): sense the
+ * ligand plane (ligand: [nx][ny], a whole unbanded plane, not written) at the
+ * agent's bin, receptor, motor, move; motil / loc ([2][ld]) are updated in
+ * place, bin_lin (and ix_out, nullable) receive the final bins.  Draw j of the
+ * agent with key k (key[a], or a when key is NULL) at inner update s is
+ * Philox(seed, counter (s, k, j, 0)); s = counter[0] + the inner index, and
+ * the call then advances counter[0] by substeps (in stream order).          */
+int vk_motility_step(const vk_motility_params *p, int64_t n_agents, int64_t ld, double dt,
+                     int32_t substeps, double *motil, double *loc, const int64_t *key,
+                     const double *ligand, int32_t nx, int32_t ny, double bound_x, double bound_y,
+                     uint64_t *counter, int32_t *bin_lin, int32_t *ix_out, vk_stream_t stream);
+
+/* Occupancy on the device: order[k] = the agent column with the k-th smallest
+ * (bin_lin[a], key[a]) (key NULL: the column index; keys distinct, < 2^32),
+ * sorted_bin[k] = its bin.  n_bins bounds bin_lin (it limits the sorted bits).
+ * scratch: 256-B aligned, scratch_bytes >= vk_occupancy_scratch_bytes(n).
+ * No host synchronisation.                                                   */
+int64_t vk_occupancy_scratch_bytes(int64_t n_agents);
+int vk_occupancy_sort(const int32_t *bin_lin, const int64_t *key, int64_t n_agents, int64_t n_bins,
+                      int32_t *order, int32_t *sorted_bin, void *scratch, int64_t scratch_bytes,
+                      vk_stream_t stream);
+
+/* vk_exchange_sorted from vk_occupancy_sort's output: one thread per sorted
+ * slot, the head of each bin's segment adds its agents' counts in segment
+ * (agent) order.  Bit-identical to vk_exchange_sorted on the host occupancy. */
+int vk_exchange_ordered(double *fields, int64_t field_stride, const int32_t *sorted_bin,
+                        const int32_t *order, int64_t n_agents, const int64_t *counts, int64_t ld,
+                        const int32_t *map_count, const int32_t *map_field, int32_t n_map,
+                        double binvol_avogadro, vk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

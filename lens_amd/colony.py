@@ -18,6 +18,13 @@ a :class:`~lens_amd.lattice.Lattice` (configs 3-4; DiffusionField + agents)
 
 Step order and quirks follow SURVEY.md Appendix A.5.
 
+With a :class:`~lens_amd.motility.MotilityModel` a lattice colony's step starts
+with the move: each agent senses the pre-step ligand plane, its receptor and
+motor update (the reference's chemoreceptor_cluster.py / coarse_motor.py), it
+runs or tumbles (this engine's kinematics, not the reference's multibody), and
+the bins and their agent-ordered occupancy are rebuilt on the device -- then
+the step above, with the exchange going into the bin the agent has reached.
+
 With a :class:`~lens_amd.cells.CellModel` the step continues like the
 reference's deriver pass: the growth process (from the step-start state),
 then TreeMass / DeriveGlobals (``mmol_to_counts`` for the next step's
@@ -38,6 +45,7 @@ from lens_amd.cells import CellModel, lineage_ids
 from lens_amd.configs import initial_conc
 from lens_amd.kinetics import KineticsEngine
 from lens_amd.lattice import Lattice, occupancy, segment_index, N_A_LEGACY
+from lens_amd.motility import DeviceOccupancy, MotilityModel, ROW_NAMES as MOTIL_ROW_NAMES, motility_step
 from lens_amd.rate_law_compiler import compile_rate_laws, RateLawTable
 
 
@@ -52,11 +60,23 @@ class Colony:
                  max_steps: int = 100000, environment='held', env_volume_L: float = 1e-14,
                  avogadro: float = N_A_LEGACY, exchange: str = 'sorted', mass_fg: float = 1339.0,
                  table: Optional[RateLawTable] = None, specialize: bool = False,
-                 cells: Optional[CellModel] = None, agent_ids=None):
+                 cells: Optional[CellModel] = None, agent_ids=None, motility: Optional[MotilityModel] = None):
         if integrator not in ('euler', 'dopri5'):
             raise ValueError('integrator must be euler or dopri5')
         if exchange not in ('sorted', 'atomic'):
             raise ValueError('exchange must be sorted or atomic')
+        if motility is not None:
+            # checked before anything is built: a motile colony moves and re-bins its
+            # agents on the device, on one whole plane (division and row bands: not yet)
+            if not isinstance(environment, Lattice):
+                raise ValueError('motility needs a Lattice environment (agents move through its ligand plane)')
+            if motility.ligand_id not in environment.molecules:
+                raise ValueError('motility: the lattice has no %r plane (molecules: %s)' % (
+                    motility.ligand_id, environment.molecules))
+            if environment.pad_top or environment.pad_bot or not (environment.edge_top and environment.edge_bot):
+                raise ValueError('motility needs a whole, unbanded plane (row bands are not supported)')
+            if cells is not None:
+                raise ValueError('motility with cells (growth and division) is not supported')
         self.config = config
         self.table = table or compile_rate_laws(config['reactions'], config['kinetic_parameters'])
         self.device = native.resolve_device(device)
@@ -111,6 +131,7 @@ class Colony:
         self.location = None
         self.env_fields = None
         self.cells = cells
+        self.motility = motility
         if cells is not None:
             rows, m2c = cells.initial_rows(ld)
             self.cell = torch.from_numpy(rows).to(dev).contiguous()
@@ -131,6 +152,12 @@ class Colony:
             self.location = z(2, ld)
             self.bin_lin = z(ld, dtype=torch.int32)
             self.bin_ix = z(ld, dtype=torch.int32)
+            if motility is not None:
+                self.motil = torch.from_numpy(motility.initial_rows(self.n, ld)).to(dev).contiguous()
+                # global inner-update index of the next motility launch (the Philox counter
+                # word): on the device, advanced by each launch, so graphs replay it
+                self._motil_counter = z(1, dtype=torch.int64)
+                self._occ_dev = DeviceOccupancy(ld, dev)
         elif environment == 'nonspatial':
             mols = []
             for e in t.external_ids + [k[1] for k in t.species if k[0] == 'external']:
@@ -193,6 +220,8 @@ class Colony:
             names.append('location')
         if self.cells is not None:
             names += ['cell', 'divide', 'lin_root', 'lin_depth', 'lin_path']
+        if getattr(self, 'motility', None) is not None:
+            names.append('motil')
         if self.ordinal is not None:
             names.append('ordinal')
         if self.env_fields is not None:
@@ -223,6 +252,8 @@ class Colony:
         lat, n = self.lattice, self.n
         if lat is None or self.cells is not None or self.router is not None or n == 0:
             return
+        if self.motility is not None:
+            return      # agents leave bin order every step: the separate launches
         if lat.pad_top or lat.pad_bot or not (lat.edge_top and lat.edge_bot):
             return
         # stored in bin order, and within a bin in the exchange's agent order
@@ -366,6 +397,8 @@ class Colony:
         timing = {k: v for k, v in (timing or {}).items() if v is not None}
         if stamp is not None:
             stamp(0)
+        if self.motility is not None:
+            self._motility_step(dt)
         if self.lattice is not None and self.overlap_kinetics:
             # kinetics + gather read only the pre-step field and agent state, so
             # they run on a side stream beside the diffusion passes; the pass
@@ -448,6 +481,8 @@ class Colony:
             raise ValueError('run() schedules a lattice colony; use step() otherwise')
         if self.cells is not None:
             raise ValueError('growth and division run with step(): their derivers fix one clock')
+        if self.motility is not None:
+            raise ValueError('a motile colony steps with step(): the move runs on the step clock')
         procs = [('diffusion', float(diffusion_dt)), ('kinetics', float(kinetics_dt))]   # store order
         front = {name: 0.0 for name, _ in procs}      # every update() call starts its fronts at 0
         pending = {}
@@ -525,10 +560,26 @@ class Colony:
                                                      self.counts, allreduce=allreduce, events=timing.get('diff'))
         return self.last_step_coupled
 
+    def _motility_step(self, dt):
+        """First in a motile colony's step: sense the pre-step ligand plane, receptor,
+        motor, move (vk_motility_step; bins come out of the kernel), then the device
+        occupancy of the new bins for the ordered exchange.  No host read and no
+        re-layout: ``_layout`` stays, captured graphs stay valid."""
+        if self.router is not None:
+            raise ValueError('a motile colony takes no router')
+        motility_step(self.motility, self.lattice, self.location, self.motil, self.n, dt, self._motil_counter,
+                      key=getattr(self, 'agent_order', None), bin_lin=self.bin_lin, bin_ix=self.bin_ix)
+        if self.exchange_mode == 'sorted' and self.map_exch_count.numel():
+            lat = self.lattice
+            self._occ_dev.sort(self.bin_lin, self.n, lat.rows_local * lat.ny, getattr(self, 'agent_order', None))
+
     def _step_exchange(self):
         lat = self.lattice
         if self.map_exch_count.numel():
-            if self.exchange_mode == 'sorted':
+            if self.motility is not None and self.exchange_mode == 'sorted':
+                lat.exchange_ordered(self._occ_dev.order, self._occ_dev.sorted_bin, self.n, self.counts,
+                                     self.map_exch_count, self.map_exch_field)
+            elif self.exchange_mode == 'sorted':
                 lat.exchange_sorted(self.occ, self.counts, self.map_exch_count, self.map_exch_field)
             else:
                 lat.exchange_atomic(self.bin_lin, self.n, self.counts, self.map_exch_count,
@@ -601,7 +652,9 @@ class Colony:
         so the colony state is unchanged until the first replay. The graph
         holds the buffers and the agent count of capture time: set_agents()
         values may change between replays (they are copied in place), but a
-        re-binning of moved agents invalidates it (replay raises).
+        re-binning of moved agents invalidates it (replay raises).  A motile
+        colony (``motility=``) moves and re-bins its agents inside the graph:
+        each replay continues the walk (the Philox counter lives on the device).
         ``steps_per_launch`` > 1 (a held colony without division) captures
         :meth:`step_many` launches of that many steps instead.
         ``stamps`` (optional, a device int64 tensor of 3 * steps) records each
@@ -626,6 +679,8 @@ class Colony:
             raise ValueError('Colony.capture: steps_per_launch must divide steps (and takes no stamps)')
         if spl > 1:
             self._step_buffers(spl)                 # allocated before the capture (graphs hold the pointers)
+        if overlap and self.motility is not None:
+            raise ValueError('Colony.capture: overlap is not available for a motile colony')
         overlap = bool(overlap) and self._overlap_ok() and spl == 1
         if overlap and (getattr(self, '_counts_alt', None) is None or self._counts_alt.shape != self.counts.shape):
             self._counts_alt = torch.zeros_like(self.counts)
@@ -909,4 +964,7 @@ class Colony:
             out['global']['width'] = np.full(self.n, self.cells.width)
             out['global']['mmol_to_counts'] = self.m2c[:self.n].cpu().numpy().copy()
             out.setdefault('internal', {})['protein'] = c[native.VK_CELL_PROTEIN].copy()
+        if self.motility is not None:
+            m = self.motil[:, :self.n].cpu().numpy()
+            out['motility'] = {name: m[row].copy() for row, name in enumerate(MOTIL_ROW_NAMES)}
         return out

@@ -23,6 +23,7 @@
 #include <vector>
 
 
+#include "vk_bin.h"
 #include "vk_internal.h"
 #include "vk_stencil_launch.h"
 
@@ -680,6 +681,48 @@ extern "C" int vk_exchange_sorted(double *fields, int64_t field_stride, const in
     return vk::launch_check("k_exchange_sorted");
 }
 
+// The same per-bin sums from a device-side occupancy (vk_occupancy_sort): thread k is
+// the head of a bin's segment iff sorted_bin[k] differs from sorted_bin[k - 1]; a head
+// walks its segment and does what k_exchange_sorted does for one bin.  No occupied-bin
+// count is needed, so nothing is read back to the host.
+__global__ __launch_bounds__(256) void k_exchange_ordered(double *__restrict__ fields, int64_t field_stride,
+                                                          const int32_t *__restrict__ sorted_bin,
+                                                          const int32_t *__restrict__ order, int n,
+                                                          const int64_t *__restrict__ counts, int64_t ld,
+                                                          const int32_t *__restrict__ map_count,
+                                                          const int32_t *__restrict__ map_field, int n_map,
+                                                          double bva) {
+    const int k0 = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k0 >= n) return;
+    const int32_t bin = sorted_bin[k0];
+    if (k0 > 0 && sorted_bin[k0 - 1] == bin) return;
+    int k1 = k0 + 1;
+    while (k1 < n && sorted_bin[k1] == bin) ++k1;
+    for (int i = 0; i < n_map; ++i) {
+        double *p = fields + (int64_t)ldc(map_field, i) * field_stride + bin;
+        const int64_t *cr = counts + (int64_t)ldc(map_count, i) * ld;
+        double v = *p;
+        for (int k = k0; k < k1; ++k) v = v + exchange_mM(cr[order[k]], bva);
+        *p = v;
+    }
+}
+
+extern "C" int vk_exchange_ordered(double *fields, int64_t field_stride, const int32_t *sorted_bin,
+                                   const int32_t *order, int64_t n, const int64_t *counts, int64_t ld,
+                                   const int32_t *map_count, const int32_t *map_field, int32_t n_map,
+                                   double binvol_avogadro, vk_stream_t stream) {
+    if (n < 0 || n >= INT32_MAX || ld < n || n_map < 0 ||
+        (n > 0 && n_map > 0 && (!fields || !sorted_bin || !order || !counts || !map_count || !map_field))) {
+        vk::set_error("vk_exchange_ordered: bad arguments");
+        return VK_ERR_ARG;
+    }
+    if (n == 0 || n_map == 0) return VK_OK;
+    hipLaunchKernelGGL(k_exchange_ordered, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       fields, field_stride, sorted_bin, order, (int)n, counts, ld, map_count, map_field, n_map,
+                       binvol_avogadro);
+    return vk::launch_check("k_exchange_ordered");
+}
+
 __global__ __launch_bounds__(256) void k_exchange_atomic(double *__restrict__ fields, int64_t field_stride,
                                                          const int32_t *__restrict__ bin_lin, int64_t n,
                                                          const int64_t *__restrict__ counts, int64_t ld,
@@ -712,23 +755,13 @@ extern "C" int vk_exchange_atomic(double *fields, int64_t field_stride, const in
     return vk::launch_check("k_exchange_atomic");
 }
 
-// get_bin_site: floor(loc * n / bound) as int, then Python/numpy floor-mod n.
-__device__ __forceinline__ int bin_axis(double loc, int n, double bound) {
-    const double v = floor(loc * n / bound);
-    if (!(fabs(v) < 9.0e15)) return 0;
-    int64_t i = (int64_t)v % n;
-    if (i < 0) i += n;
-    return (int)i;
-}
-
 __global__ __launch_bounds__(256) void k_bin_sites(const double *__restrict__ loc, int64_t n, int64_t ld, int nx,
                                                    int ny, double bx, double by, int row_offset,
                                                    int32_t *__restrict__ bin_lin, int32_t *__restrict__ ix_out) {
     const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= n) return;
-    const int ix = bin_axis(loc[a], nx, bx);
-    const int iy = bin_axis(loc[ld + a], ny, by);
-    bin_lin[a] = (ix - row_offset) * ny + iy;
+    int ix;
+    bin_lin[a] = bin_site_lin(loc[a], loc[ld + a], nx, ny, bx, by, row_offset, &ix);
     if (ix_out) ix_out[a] = ix;
 }
 

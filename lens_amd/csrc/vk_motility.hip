@@ -1,0 +1,179 @@
+// Motile agents on MI355X (gfx950): chemoreceptor cluster, flagellar motor and a
+// run-and-tumble move, one thread per agent, `substeps` inner updates per call.
+//
+// Reference semantics, restated in the reference's operation order (compiled with
+// -ffp-contract=off, so the +, -, x, / sequences round as the reference's Python does;
+// log / exp / sin / cos are the device library's, within an ulp or two of libm's):
+//   ReceptorCluster.next_update   vivarium/processes/chemoreceptor_cluster.py:166-209
+//   MotorActivity.next_update     vivarium/processes/coarse_motor.py:134-164 (+ run / tumble :177-190)
+// The reference converts CheR / CheB from mM to uM through pint
+// (`.to('umol/L').magnitude`).  pint was not available when this was written, so the factor
+// is taken as x * 1e3 and is NOT pinned against the reference's units library.
+// Where the reference's motor raises a math domain error (a switching rate r >= 1 makes
+// log(1 - r) undefined) the switch probability here is 1.
+//
+// NOT reference parity: the kinematics.  The reference hands thrust and torque to a pymunk
+// rigid-body simulation (multibody); this engine has no multibody physics, and moves each
+// agent with its own stand-in: a constant run speed along the heading, a slower drift and a
+// Gaussian heading change while tumbling, reflecting walls.  thrust / torque are still
+// emitted (250 / 0 running, 100 / d(angle)/dt tumbling).
+//
+// Random numbers: draw j in {0, 1, 2} of the agent with reference-order key k at global
+// inner update s is philox_uniform(seed, s, k, 0, j) -- independent of storage order and
+// launch geometry.  s comes from a one-element device counter that the launch sequence
+// advances by `substeps`, so a captured graph replays successive steps.
+//
+// A streaming kernel: per agent it reads and writes 9 state rows and the location once, and
+// reads one ligand value per inner update; the state of an agent lives in registers between.
+
+#include <math.h>
+#include <stdint.h>
+
+#include "vk_bin.h"
+#include "vk_internal.h"
+#include "vk_philox.h"
+
+__global__ __launch_bounds__(256) void k_motility_step(vk_motility_params p, int64_t n, int64_t ld, double h,
+                                                       int substeps, double *__restrict__ motil,
+                                                       double *__restrict__ loc, const int64_t *__restrict__ key,
+                                                       const double *__restrict__ ligand, int nx, int ny, double bx,
+                                                       double by, double bx_below, double by_below,
+                                                       const uint64_t *__restrict__ counter,
+                                                       int32_t *__restrict__ bin_lin, int32_t *__restrict__ ix_out) {
+    const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= n) return;
+    const int32_t k = key ? (int32_t)key[a] : (int32_t)a;
+    const uint64_t s0 = counter[0];
+    double n_methyl = motil[(int64_t)VK_MOTIL_N_METHYL * ld + a];
+    double P_on = motil[(int64_t)VK_MOTIL_ACTIVITY * ld + a];
+    double CheY_P = motil[(int64_t)VK_MOTIL_CHEY_P * ld + a];
+    double ccw_motor_bias = motil[(int64_t)VK_MOTIL_CCW_MOTOR_BIAS * ld + a];
+    double ccw_to_cw = motil[(int64_t)VK_MOTIL_CCW_TO_CW * ld + a];
+    bool tumbling = motil[(int64_t)VK_MOTIL_MOTOR_STATE * ld + a] != 0.0;
+    double angle = motil[(int64_t)VK_MOTIL_ANGLE * ld + a];
+    double thrust = motil[(int64_t)VK_MOTIL_THRUST * ld + a];
+    double torque = motil[(int64_t)VK_MOTIL_TORQUE * ld + a];
+    double x = loc[a], y = loc[ld + a];
+    int ix;
+    int32_t bin = bin_site_lin(x, y, nx, ny, bx, by, 0, &ix);
+    // mM -> uM (see the header: the reference's pint conversion, unpinned)
+    const double CheR = p.CheR * 1e3, CheB = p.CheB * 1e3;
+    for (int s = 0; s < substeps; ++s) {
+        // (a) sense: the plane is not written here, so this is the pre-step field
+        const double L = ligand[bin];
+
+        // (b) receptor.  The reference's quirk is kept: an out-of-range n_methyl is
+        // clamped and not advanced in that update
+        if (n_methyl < 0.0) {
+            n_methyl = 0.0;
+        } else if (n_methyl > 8.0) {
+            n_methyl = 8.0;
+        } else {
+            const double d_methyl = p.adapt_rate * (p.k_meth * CheR * (1.0 - P_on) - p.k_demeth * CheB * P_on) * h;
+            n_methyl += d_methyl;
+        }
+        double offset_energy;
+        if (n_methyl < 0.0) offset_energy = 1.0;
+        else if (n_methyl < 2.0) offset_energy = 1.0 - 0.5 * n_methyl;
+        else if (n_methyl < 4.0) offset_energy = -0.3 * (n_methyl - 2.0);
+        else if (n_methyl < 6.0) offset_energy = -0.6 - 0.25 * (n_methyl - 4.0);
+        else if (n_methyl < 7.0) offset_energy = -1.1 - 0.9 * (n_methyl - 6.0);
+        else if (n_methyl < 8.0) offset_energy = -2.0 - (n_methyl - 7.0);
+        else offset_energy = -3.0;
+        const double Tar = p.n_Tar * (offset_energy + log((1.0 + L / p.K_Tar_off) / (1.0 + L / p.K_Tar_on)));
+        const double Tsr = p.n_Tsr * (offset_energy + log((1.0 + L / p.K_Tsr_off) / (1.0 + L / p.K_Tsr_on)));
+        P_on = 1.0 / (1.0 + exp(Tar + Tsr));
+
+        // (c) motor, from the activity just computed
+        CheY_P = p.adapt_precision * p.k_y * p.k_s * P_on / (p.k_y * p.k_s * P_on + p.k_z + p.gamma_Y);
+        ccw_motor_bias = p.mb_0 / (CheY_P * (1.0 - p.mb_0) + p.mb_0);
+        ccw_to_cw = p.cw_to_ccw * (1.0 / ccw_motor_bias - 1.0);
+        if (ccw_to_cw < p.cw_to_ccw_leak) ccw_to_cw = p.cw_to_ccw_leak;
+        const double r = tumbling ? p.cw_to_ccw : ccw_to_cw;
+        double prob_switch = 1.0;
+        if (r < 1.0) {
+            const double rate = -log(1.0 - r);
+            prob_switch = 1.0 - exp(-rate * h);
+        }
+        const uint64_t step = s0 + (uint64_t)s;
+        if (philox_uniform(p.seed, step, k, 0, 0) <= prob_switch) tumbling = !tumbling;
+
+        // (d) kinematics: this engine's stand-in for the reference's pymunk multibody
+        double speed;
+        if (tumbling) {
+            const double u1 = philox_uniform(p.seed, step, k, 0, 1);
+            const double u2 = philox_uniform(p.seed, step, k, 0, 2);
+            const double z = sqrt(-2.0 * log(1.0 - u1)) * cos(6.283185307179586 * u2);   // Box-Muller
+            const double d_angle = p.tumble_sigma * h * z;
+            angle += d_angle;
+            speed = p.run_speed * 100.0 / 250.0;
+            thrust = 100.0;
+            torque = d_angle / h;
+        } else {
+            speed = p.run_speed;
+            thrust = 250.0;
+            torque = 0.0;
+        }
+        x += speed * h * cos(angle);
+        y += speed * h * sin(angle);
+        // reflecting walls: mirror the coordinate and the heading, then clamp into [0, bound)
+        if (x < 0.0) {
+            x = -x;
+            angle = M_PI - angle;
+        } else if (x >= bx) {
+            x = 2.0 * bx - x;
+            angle = M_PI - angle;
+        }
+        if (y < 0.0) {
+            y = -y;
+            angle = -angle;
+        } else if (y >= by) {
+            y = 2.0 * by - y;
+            angle = -angle;
+        }
+        x = fmin(fmax(x, 0.0), bx_below);
+        y = fmin(fmax(y, 0.0), by_below);
+        bin = bin_site_lin(x, y, nx, ny, bx, by, 0, &ix);
+    }
+    motil[(int64_t)VK_MOTIL_N_METHYL * ld + a] = n_methyl;
+    motil[(int64_t)VK_MOTIL_ACTIVITY * ld + a] = P_on;
+    motil[(int64_t)VK_MOTIL_CHEY_P * ld + a] = CheY_P;
+    motil[(int64_t)VK_MOTIL_CCW_MOTOR_BIAS * ld + a] = ccw_motor_bias;
+    motil[(int64_t)VK_MOTIL_CCW_TO_CW * ld + a] = ccw_to_cw;
+    motil[(int64_t)VK_MOTIL_MOTOR_STATE * ld + a] = tumbling ? 1.0 : 0.0;
+    motil[(int64_t)VK_MOTIL_ANGLE * ld + a] = angle;
+    motil[(int64_t)VK_MOTIL_THRUST * ld + a] = thrust;
+    motil[(int64_t)VK_MOTIL_TORQUE * ld + a] = torque;
+    loc[a] = x;
+    loc[ld + a] = y;
+    bin_lin[a] = bin;
+    if (ix_out) ix_out[a] = ix;
+}
+
+// after the agents' kernel, in stream order: the next call's first inner update
+__global__ void k_motility_advance(uint64_t *counter, uint64_t by) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) counter[0] += by;
+}
+
+extern "C" int vk_motility_step(const vk_motility_params *p, int64_t n, int64_t ld, double dt, int32_t substeps,
+                                double *motil, double *loc, const int64_t *key, const double *ligand, int32_t nx,
+                                int32_t ny, double bound_x, double bound_y, uint64_t *counter, int32_t *bin_lin,
+                                int32_t *ix_out, vk_stream_t stream) {
+    if (!p || n < 0 || ld < n || substeps < 1 || !(dt > 0.0) || nx <= 0 || ny <= 0 || !(bound_x > 0.0) ||
+        !(bound_y > 0.0) || (int64_t)nx * ny >= INT32_MAX || !counter ||
+        (n > 0 && (!motil || !loc || !ligand || !bin_lin))) {
+        vk::set_error("vk_motility_step: bad arguments");
+        return VK_ERR_ARG;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (n > 0) {
+        hipLaunchKernelGGL(k_motility_step, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, *p, n, ld,
+                           dt / substeps, substeps, motil, loc, key, ligand, nx, ny, bound_x, bound_y,
+                           nextafter(bound_x, 0.0), nextafter(bound_y, 0.0), counter, bin_lin, ix_out);
+        const int rc = vk::launch_check("k_motility_step");
+        if (rc) return rc;
+    }
+    // the counter advances for an empty colony too: s counts inner updates, not agents
+    hipLaunchKernelGGL(k_motility_advance, dim3(1), dim3(64), 0, s, counter, (uint64_t)substeps);
+    return vk::launch_check("k_motility_advance");
+}

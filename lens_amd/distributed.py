@@ -148,6 +148,9 @@ class AgentRouter:
 
     def __init__(self, col, rank: int, world: int, group=None, agent_offset: int = None):
         self.col, self.rank, self.world, self.group = col, rank, world, group
+        if getattr(col, 'motility', None) is not None:
+            raise ValueError('AgentRouter: a motile colony (Colony(motility=...)) takes no router: its agents '
+                             'move and re-bin on one device, on a whole plane')
         lat = col.lattice
         bands = row_bands(lat.n_bins[0], world)
         if (lat.row_lo_global, lat.row_hi_global) != bands[rank]:

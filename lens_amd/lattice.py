@@ -417,6 +417,14 @@ class Lattice:
             native.ptr(map_count), native.ptr(map_field), int(map_count.numel()),
             self.binvol_avogadro, native.stream_handle()), 'vk_exchange_sorted')
 
+    def exchange_ordered(self, order, sorted_bin, n_agents, counts, map_count, map_field):
+        """:meth:`exchange_sorted` from a device occupancy (vk_occupancy_sort's
+        ``order`` / ``sorted_bin``): the same sums in the same agent order, no host read."""
+        native.check(native._lib.vk_exchange_ordered(
+            native.ptr(self.fields), self.field_stride, native.ptr(sorted_bin), native.ptr(order), n_agents,
+            native.ptr(counts), counts.shape[1], native.ptr(map_count), native.ptr(map_field),
+            int(map_count.numel()), self.binvol_avogadro, native.stream_handle()), 'vk_exchange_ordered')
+
     def exchange_atomic(self, bin_lin, n_agents, counts, map_count, map_field):
         native.check(native._lib.vk_exchange_atomic(
             native.ptr(self.fields), self.field_stride, native.ptr(bin_lin), n_agents,

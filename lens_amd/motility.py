@@ -1,0 +1,189 @@
+"""Motile agents: the reference's chemotaxis processes, batched.
+
+:class:`MotilityModel` holds what the reference's ``ReceptorCluster``
+(vivarium/processes/chemoreceptor_cluster.py) and ``MotorActivity``
+(vivarium/processes/coarse_motor.py) hold -- their default parameters and
+initial states, the receptor run to its steady state at the initial ligand
+concentration -- and the two constants of this engine's kinematics.  A
+``Colony(..., motility=model)`` then moves its agents every step on the
+device (vk_motility_step) and re-bins them there (vk_occupancy_sort,
+vk_exchange_ordered): no host read, no re-layout, so the step can be captured.
+
+Receptor and motor follow the reference's arithmetic.  The move itself does
+NOT: the reference hands thrust and torque to pymunk (multibody), which this
+engine does not have.  Agents run at ``run_speed`` along their heading, drift
+at 100/250 of it while tumbling with a Gaussian heading change of
+``tumble_sigma`` rad/s, and reflect off the lattice bounds.
+"""
+
+from __future__ import annotations
+
+import ctypes
+import math
+from typing import Optional
+
+import numpy as np
+
+from lens_amd import native
+
+STEADY_STATE_DELTA = 1e-6
+
+# ReceptorCluster.defaults + INITIAL_INTERNAL_STATE (chemoreceptor_cluster.py:22-28, :98-114)
+RECEPTOR_DEFAULTS = {
+    'n_Tar': 6, 'n_Tsr': 12,
+    'K_Tar_off': 0.02, 'K_Tar_on': 0.5, 'K_Tsr_off': 100.0, 'K_Tsr_on': 10e6,
+    'k_meth': 0.0625, 'k_demeth': 0.0714, 'adapt_rate': 1.2,
+    'CheR': 0.00016, 'CheB': 0.00028,               # mM
+    'n_methyl': 2.0, 'chemoreceptor_activity': 1. / 3.,
+}
+# MotorActivity.defaults (coarse_motor.py:51-86)
+MOTOR_DEFAULTS = {
+    'k_y': 100.0, 'k_z': 30.0, 'gamma_Y': 0.1, 'k_s': 0.45, 'adapt_precision': 3,
+    'mb_0': 0.65, 'cw_to_ccw': 0.83, 'cw_to_ccw_leak': 0.25,
+    'CheY_P': 0.5, 'ccw_motor_bias': 0.5, 'ccw_to_cw': 0.5, 'motor_state': 1, 'thrust': 0, 'torque': 0,
+}
+
+ROW_NAMES = ('n_methyl', 'chemoreceptor_activity', 'CheY_P', 'ccw_motor_bias', 'ccw_to_cw', 'motor_state',
+             'angle', 'thrust', 'torque')          # vk_motil_row order
+
+
+def receptor_update(p, n_methyl, P_on, ligand, timestep):
+    """ReceptorCluster.next_update (chemoreceptor_cluster.py:166-209) on plain
+    floats; CheR / CheB mM -> uM as x * 1e3 (the reference converts through
+    pint, which this restatement is not pinned against)."""
+    CheR, CheB = p['CheR'] * 1e3, p['CheB'] * 1e3
+    if n_methyl < 0:
+        n_methyl = 0
+    elif n_methyl > 8:
+        n_methyl = 8
+    else:
+        n_methyl += p['adapt_rate'] * (p['k_meth'] * CheR * (1.0 - P_on) - p['k_demeth'] * CheB * P_on) * timestep
+    if n_methyl < 0:
+        eps = 1.0
+    elif n_methyl < 2:
+        eps = 1.0 - 0.5 * n_methyl
+    elif n_methyl < 4:
+        eps = -0.3 * (n_methyl - 2.0)
+    elif n_methyl < 6:
+        eps = -0.6 - 0.25 * (n_methyl - 4.0)
+    elif n_methyl < 7:
+        eps = -1.1 - 0.9 * (n_methyl - 6.0)
+    elif n_methyl < 8:
+        eps = -2.0 - (n_methyl - 7.0)
+    else:
+        eps = -3.0
+    tar = p['n_Tar'] * (eps + math.log((1 + ligand / p['K_Tar_off']) / (1 + ligand / p['K_Tar_on'])))
+    tsr = p['n_Tsr'] * (eps + math.log((1 + ligand / p['K_Tsr_off']) / (1 + ligand / p['K_Tsr_on'])))
+    return n_methyl, 1.0 / (1.0 + math.exp(tar + tsr))
+
+
+class MotilityModel:
+    def __init__(self, ligand_id: str = 'MeAsp', initial_ligand: float = 5.0, receptor: Optional[dict] = None,
+                 motor: Optional[dict] = None, run_speed: float = 14.0, tumble_sigma: float = math.radians(120.0),
+                 substeps: int = 1, seed: int = 0, angles=None):
+        for given, known, what in ((receptor, RECEPTOR_DEFAULTS, 'receptor'), (motor, MOTOR_DEFAULTS, 'motor')):
+            unknown = set(given or {}) - set(known)
+            if unknown:
+                raise ValueError('unknown %s parameters: %s' % (what, sorted(unknown)))
+        if int(substeps) < 1:
+            raise ValueError('substeps >= 1')
+        self.ligand_id = ligand_id
+        self.initial_ligand = float(initial_ligand)
+        self.receptor = dict(RECEPTOR_DEFAULTS, **(receptor or {}))
+        self.motor = dict(MOTOR_DEFAULTS, **(motor or {}))
+        self.run_speed = float(run_speed)        # um/s: the speed the reference's timelines assume
+        self.tumble_sigma = float(tumble_sigma)  # rad/s
+        self.substeps = int(substeps)
+        self.seed = int(seed)
+        self.angles = angles                     # initial headings (rad) per agent; None: seeded uniform
+        # run_to_steady_state(self, initial_state, 1.0) (chemoreceptor_cluster.py:36-46, :126)
+        n_methyl, P_on = self.receptor['n_methyl'], self.receptor['chemoreceptor_activity']
+        delta, self.steady_iterations = 1, 0
+        while delta > STEADY_STATE_DELTA:
+            nm, po = receptor_update(self.receptor, n_methyl, P_on, self.initial_ligand, 1.0)
+            delta = ((P_on - po) ** 2 + (n_methyl - nm) ** 2) ** 0.5
+            n_methyl, P_on = nm, po
+            self.steady_iterations += 1
+        self.n_methyl, self.chemoreceptor_activity = n_methyl, P_on
+
+    def initial_rows(self, n: int, ld: int, angles=None) -> np.ndarray:
+        """motil[VK_MOTIL_ROWS][ld]: the receptor at its steady state, the motor
+        rows from MotorActivity's initial_state, headings from ``angles`` or
+        uniform in [0, 2 pi) from a numpy generator seeded with the model's seed."""
+        rows = np.zeros((native.VK_MOTIL_ROWS, ld))
+        m = self.motor
+        for name, value in (('n_methyl', self.n_methyl), ('chemoreceptor_activity', self.chemoreceptor_activity),
+                            ('CheY_P', m['CheY_P']), ('ccw_motor_bias', m['ccw_motor_bias']),
+                            ('ccw_to_cw', m['ccw_to_cw']), ('motor_state', m['motor_state']),
+                            ('thrust', m['thrust']), ('torque', m['torque'])):
+            rows[ROW_NAMES.index(name), :n] = value
+        if angles is None:
+            angles = self.angles
+        if angles is None:
+            angles = np.random.default_rng(self.seed).uniform(0.0, 2.0 * math.pi, n)
+        angles = np.asarray(angles, dtype=np.float64)
+        if angles.shape[0] < n:
+            raise ValueError('angles must give every agent a heading (%d < %d)' % (angles.shape[0], n))
+        rows[native.VK_MOTIL_ANGLE, :n] = angles[:n]
+        return rows
+
+    def vk_params(self) -> native.VkMotilityParams:
+        p = native.VkMotilityParams()
+        for name in ('n_Tar', 'n_Tsr', 'K_Tar_off', 'K_Tar_on', 'K_Tsr_off', 'K_Tsr_on', 'k_meth', 'k_demeth',
+                     'adapt_rate', 'CheR', 'CheB'):
+            setattr(p, name, float(self.receptor[name]))
+        for name in ('k_y', 'k_s', 'k_z', 'gamma_Y', 'adapt_precision', 'mb_0', 'cw_to_ccw', 'cw_to_ccw_leak'):
+            setattr(p, name, float(self.motor[name]))
+        p.run_speed, p.tumble_sigma, p.seed = self.run_speed, self.tumble_sigma, self.seed
+        return p
+
+
+def motility_step(model: MotilityModel, lattice, location, motil, n: int, dt: float, counter, key=None,
+                  bin_lin=None, bin_ix=None, substeps: Optional[int] = None):
+    """One vk_motility_step launch on the current stream: ``model.substeps``
+    inner updates of ``dt / substeps`` for agents [0, n) of ``location`` [2, ld]
+    and ``motil`` [VK_MOTIL_ROWS, ld]; ``counter`` (one device int64) supplies
+    the inner-update index and is advanced.  ``bin_lin`` / ``bin_ix`` (int32
+    [ld]) receive the bins.  The lattice must hold whole, unbanded planes."""
+    import torch
+    if lattice.pad_top or lattice.pad_bot or not (lattice.edge_top and lattice.edge_bot):
+        raise ValueError('motility_step: a whole, unbanded plane')
+    ld = location.shape[1]
+    if motil.shape != (native.VK_MOTIL_ROWS, ld) or not (motil.is_contiguous() and location.is_contiguous()):
+        raise ValueError('motility_step: motil must be [VK_MOTIL_ROWS, ld] beside location [2, ld], contiguous')
+    if bin_lin is None:
+        bin_lin = torch.zeros(ld, dtype=torch.int32, device=location.device)
+    plane = lattice.fields[lattice.molecules.index(model.ligand_id)]
+    p = model.vk_params()
+    native.check(native._lib.vk_motility_step(
+        ctypes.byref(p), n, ld, float(dt), int(model.substeps if substeps is None else substeps), native.ptr(motil),
+        native.ptr(location), native.ptr(key), native.ptr(plane), lattice.n_bins[0], lattice.n_bins[1],
+        lattice.bounds[0], lattice.bounds[1], native.ptr(counter), native.ptr(bin_lin), native.ptr(bin_ix),
+        native.stream_handle()), 'vk_motility_step')
+    return bin_lin
+
+
+class DeviceOccupancy:
+    """Buffers of vk_occupancy_sort for up to ``ld`` agents: ``order`` and
+    ``sorted_bin`` (int32 [ld]) and the sort's scratch, allocated once so that
+    a captured graph keeps valid pointers."""
+
+    def __init__(self, ld: int, device):
+        import torch
+        self.order = torch.zeros(ld, dtype=torch.int32, device=device)
+        self.sorted_bin = torch.zeros(ld, dtype=torch.int32, device=device)
+        nbytes = int(native._lib.vk_occupancy_scratch_bytes(ld))
+        self.scratch = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
+        self._off = (-self.scratch.data_ptr()) % 256     # the sort wants a 256-B aligned base
+        self._bytes = nbytes
+
+    def sort(self, bin_lin, n: int, n_bins: int, key=None):
+        """order / sorted_bin [:n] := the agents by (bin, key) -- what
+        lattice.occupancy computes on the host, without a host read."""
+        if n > self.order.numel():
+            raise ValueError('DeviceOccupancy: more agents than the buffers hold')
+        native.check(native._lib.vk_occupancy_sort(
+            native.ptr(bin_lin), native.ptr(key), n, int(n_bins), native.ptr(self.order),
+            native.ptr(self.sorted_bin), self.scratch.data_ptr() + self._off, self._bytes,
+            native.stream_handle()), 'vk_occupancy_sort')
+        return self.order, self.sorted_bin

@@ -31,11 +31,15 @@ EXPORTS = (
     'vk_timestamp', 'vk_wall_clock_khz', 'vk_copy_stream', 'vk_gather', 'vk_exchange_sorted',
     'vk_exchange_atomic', 'vk_bin_sites', 'vk_cell_step', 'vk_divide_scratch_bytes', 'vk_divide_plan',
     'vk_divide_gather', 'vk_divide_lineage', 'vk_divide_locations', 'vk_kremling_step',
-    'vk_expression_step',
+    'vk_expression_step', 'vk_motility_step', 'vk_occupancy_scratch_bytes', 'vk_occupancy_sort',
+    'vk_exchange_ordered',
 )
 
 VK_CELL_MASS, VK_CELL_VOLUME, VK_CELL_LENGTH, VK_CELL_SURFACE_AREA, VK_CELL_PROTEIN, VK_CELL_ANGLE = range(6)
 VK_CELL_ROWS = 6
+(VK_MOTIL_N_METHYL, VK_MOTIL_ACTIVITY, VK_MOTIL_CHEY_P, VK_MOTIL_CCW_MOTOR_BIAS, VK_MOTIL_CCW_TO_CW,
+ VK_MOTIL_MOTOR_STATE, VK_MOTIL_ANGLE, VK_MOTIL_THRUST, VK_MOTIL_TORQUE) = range(9)
+VK_MOTIL_ROWS = 9
 VK_GROWTH_PROTEIN, VK_GROWTH_MASS = 0, 1
 VK_RNG_STREAM, VK_RNG_PHILOX = 0, 1
 VK_DIVIDE_SET, VK_DIVIDE_SPLIT, VK_DIVIDE_ZERO = 0, 1, 2
@@ -86,6 +90,13 @@ class VkKremlingParams(ctypes.Structure):
         'mw3', 'Y1_sim', 'Y2_sim', 'Y3_sim', 'K', 'kb', 'ksyn', 'KI')]
 
 
+class VkMotilityParams(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_double) for n in (
+        'n_Tar', 'n_Tsr', 'K_Tar_off', 'K_Tar_on', 'K_Tsr_off', 'K_Tsr_on', 'k_meth', 'k_demeth', 'adapt_rate',
+        'CheR', 'CheB', 'k_y', 'k_s', 'k_z', 'gamma_Y', 'adapt_precision', 'mb_0', 'cw_to_ccw',
+        'cw_to_ccw_leak', 'run_speed', 'tumble_sigma')] + [('seed', ctypes.c_uint64)]
+
+
 _SIGS = {
     'vk_abi_version': ([], ctypes.c_int),
     'vk_last_error': ([], ctypes.c_char_p),
@@ -130,6 +141,11 @@ _SIGS = {
     'vk_expression_step': ([_vp, _i64, _i64, _f64, _vp, _vp, _vp, _i32, _vp], ctypes.c_int),
     'vk_kremling_step': ([ctypes.POINTER(VkKremlingParams), _i64, _i64, _f64, _f64, _i32, _f64, _f64, _i32,
                           _vp, _vp, _f64, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+    'vk_motility_step': ([ctypes.POINTER(VkMotilityParams), _i64, _i64, _f64, _i32, _vp, _vp, _vp, _vp, _i32, _i32,
+                          _f64, _f64, _vp, _vp, _vp, _vp], ctypes.c_int),
+    'vk_occupancy_scratch_bytes': ([_i64], ctypes.c_int64),
+    'vk_occupancy_sort': ([_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp], ctypes.c_int),
+    'vk_exchange_ordered': ([_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _f64, _vp], ctypes.c_int),
 }
 
 _lib = None
