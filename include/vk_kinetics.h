@@ -34,6 +34,9 @@
  *       applied once per agent by Store.apply_update.
  *   vk_bin_sites
  *       replaces get_bin_site (vivarium/library/lattice_utils.py:18-40).
+ *   vk_cell_step / vk_divide_*, vk_kremling_step, vk_expression_step,
+ *   vk_motility_step, vk_contact_step
+ *       are introduced by the comment blocks above their declarations.
  *
  * Conventions
  *   - All array arguments are DEVICE pointers except vk_table_desc's, which are
@@ -618,6 +621,66 @@ int vk_exchange_ordered(double *fields, int64_t field_stride, const int32_t *sor
                         const int32_t *order, int64_t n_agents, const int64_t *counts, int64_t ld,
                         const int32_t *map_count, const int32_t *map_field, int32_t n_map,
                         double binvol_avogadro, vk_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Colony mechanics: capsule contacts on a neighbour grid
+ *
+ *   vk_contact_step
+ *       stands where the reference runs its `multibody` process
+ *       (vivarium/processes/multibody_physics.py, a pymunk rigid-body
+ *       simulation).  The contact model is THIS ENGINE'S OWN -- a Jacobi
+ *       relaxation of capsule overlaps -- and no parity with pymunk's
+ *       trajectories is claimed.  The capsules are the reference's: length
+ *       and width as DeriveGlobals gives them, centre and angle as division
+ *       places the daughters.
+ *
+ * Agent i is a capsule of centre (x, y), axis angle theta, total length L and
+ * width w: radius r = w / 2, spine half-length h = max(L - w, 0) / 2.  One
+ * iteration moves every agent from one snapshot of all agents: for each
+ * neighbour j (ascending (grid cell, key) order) whose spine comes closer than
+ * 2 r, overlap delta, it adds 0.5 * stiffness * delta along the contact normal
+ * and the turn of that push about its centre times 12 / L^2; the summed push is
+ * capped at max_push, the turn at +-max_turn; Gaussian jitter (jitter um on x
+ * and y, jitter_angle rad) is added when either is non-zero; the centre is
+ * clamped into [0, bound).  lens_amd/csrc/vk_contact.hip states every formula.
+ * ------------------------------------------------------------------------- */
+
+typedef struct vk_contact_params {
+    int32_t iterations;                  /* relaxation iterations per call, >= 1       */
+    int32_t gx, gy;                      /* neighbour grid: max(1, floor(bound / max_length)) per axis */
+    int32_t reserved;
+    double stiffness;                    /* (0, 1]: the share of an overlap removed per iteration */
+    double max_length;                   /* um: no agent is longer (bit 0 of flags otherwise) */
+    double width;                        /* um, every agent's                          */
+    double length;                       /* um, every agent's when length is NULL      */
+    double max_push;                     /* um per iteration                           */
+    double max_turn;                     /* rad per iteration                          */
+    double jitter, jitter_angle;         /* um, rad: standard deviations per iteration */
+    uint64_t seed;                       /* Philox key                                 */
+} vk_contact_params;
+
+/* Scratch of vk_contact_step for n agents on a grid of n_grid_cells = gx * gy. */
+int64_t vk_contact_scratch_bytes(int64_t n_agents, int64_t n_grid_cells);
+
+/* p->iterations relaxation iterations for agents [0, n): location ([2][ld])
+ * and angle ([ld]) are updated in place; length ([ld], NULL: p->length) is
+ * read.  key (NULL: the column index; distinct, < 2^32) fixes the neighbour
+ * order and the jitter draws, so results do not depend on the storage order.
+ * Jitter draw j of key k at iteration s is Philox(seed + depth word 1, counter
+ * (s, k, j, 0)); s = counter[0] + the iteration index, and the call then
+ * advances counter[0] by p->iterations (in stream order).  flags: one int32;
+ * bit 0 is ORed in when an agent is longer than a grid cell's edge (the 3 x 3
+ * search may then miss contacts; the call still runs).  bin_lin (and bin_ix,
+ * nullable) receive vk_bin_sites' bins of the final locations on the nx x ny
+ * lattice of bound_x x bound_y (a whole, unbanded plane).  scratch: 256-B
+ * aligned, >= vk_contact_scratch_bytes(n, gx * gy).  Argument errors return
+ * VK_ERR_ARG and launch nothing; n == 0 returns VK_OK.  No host
+ * synchronisation: the call can be captured into a graph.                   */
+int vk_contact_step(const vk_contact_params *p, int64_t n_agents, int64_t ld, double *location,
+                    double *angle, const double *length, const int64_t *key, uint64_t *counter,
+                    int32_t *flags, int32_t nx, int32_t ny, double bound_x, double bound_y,
+                    int32_t *bin_lin, int32_t *bin_ix, void *scratch, int64_t scratch_bytes,
+                    vk_stream_t stream);
 
 #ifdef __cplusplus
 }

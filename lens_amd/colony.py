@@ -25,6 +25,13 @@ runs or tumbles (this engine's kinematics, not the reference's multibody), and
 the bins and their agent-ordered occupancy are rebuilt on the device -- then
 the step above, with the exchange going into the bin the agent has reached.
 
+With a :class:`~lens_amd.mechanics.ContactModel` (``mechanics=``) the step starts
+with the contact launch instead: overlapping capsules push each other apart
+(this engine's own contact model, standing where the reference runs its pymunk
+multibody), and the bins and their occupancy are rebuilt on the device in the
+same way.  It combines with ``cells=``: growth and division then produce an
+expanding colony instead of a pile of overlapping daughters.
+
 With a :class:`~lens_amd.cells.CellModel` the step continues like the
 reference's deriver pass: the growth process (from the step-start state),
 then TreeMass / DeriveGlobals (``mmol_to_counts`` for the next step's
@@ -45,6 +52,7 @@ from lens_amd.cells import CellModel, lineage_ids
 from lens_amd.configs import initial_conc
 from lens_amd.kinetics import KineticsEngine
 from lens_amd.lattice import Lattice, occupancy, segment_index, N_A_LEGACY
+from lens_amd.mechanics import ContactBuffers, ContactModel, contact_step
 from lens_amd.motility import DeviceOccupancy, MotilityModel, ROW_NAMES as MOTIL_ROW_NAMES, motility_step
 from lens_amd.rate_law_compiler import compile_rate_laws, RateLawTable
 
@@ -60,7 +68,8 @@ class Colony:
                  max_steps: int = 100000, environment='held', env_volume_L: float = 1e-14,
                  avogadro: float = N_A_LEGACY, exchange: str = 'sorted', mass_fg: float = 1339.0,
                  table: Optional[RateLawTable] = None, specialize: bool = False,
-                 cells: Optional[CellModel] = None, agent_ids=None, motility: Optional[MotilityModel] = None):
+                 cells: Optional[CellModel] = None, agent_ids=None, motility: Optional[MotilityModel] = None,
+                 mechanics: Optional[ContactModel] = None):
         if integrator not in ('euler', 'dopri5'):
             raise ValueError('integrator must be euler or dopri5')
         if exchange not in ('sorted', 'atomic'):
@@ -77,6 +86,18 @@ class Colony:
                 raise ValueError('motility needs a whole, unbanded plane (row bands are not supported)')
             if cells is not None:
                 raise ValueError('motility with cells (growth and division) is not supported')
+        if mechanics is not None:
+            # checked before anything is built, like motility: the contact launch moves and
+            # re-bins the agents on the device, on one whole plane
+            if not isinstance(environment, Lattice):
+                raise ValueError('mechanics needs a Lattice environment (capsules move on its plane)')
+            if environment.pad_top or environment.pad_bot or not (environment.edge_top and environment.edge_bot):
+                raise ValueError('mechanics needs a whole, unbanded plane (row bands are not supported)')
+            if motility is not None:
+                raise ValueError('mechanics with motility is not supported (two writers of position and heading)')
+            if cells is not None and float(cells.width) != mechanics.width:
+                raise ValueError('mechanics: the ContactModel\'s width (%r) must equal the CellModel\'s (%r)' % (
+                    mechanics.width, cells.width))
         self.config = config
         self.table = table or compile_rate_laws(config['reactions'], config['kinetic_parameters'])
         self.device = native.resolve_device(device)
@@ -132,6 +153,7 @@ class Colony:
         self.env_fields = None
         self.cells = cells
         self.motility = motility
+        self.mechanics = mechanics
         if cells is not None:
             rows, m2c = cells.initial_rows(ld)
             self.cell = torch.from_numpy(rows).to(dev).contiguous()
@@ -158,6 +180,10 @@ class Colony:
                 # word): on the device, advanced by each launch, so graphs replay it
                 self._motil_counter = z(1, dtype=torch.int64)
                 self._occ_dev = DeviceOccupancy(ld, dev)
+            if mechanics is not None:
+                if cells is None:
+                    self.mech_angle = torch.from_numpy(mechanics.initial_angles(self.n, ld)).to(dev).contiguous()
+                self._mech_buffers()
         elif environment == 'nonspatial':
             mols = []
             for e in t.external_ids + [k[1] for k in t.species if k[0] == 'external']:
@@ -222,6 +248,8 @@ class Colony:
             names += ['cell', 'divide', 'lin_root', 'lin_depth', 'lin_path']
         if getattr(self, 'motility', None) is not None:
             names.append('motil')
+        if getattr(self, 'mechanics', None) is not None and self.cells is None:
+            names.append('mech_angle')
         if self.ordinal is not None:
             names.append('ordinal')
         if self.env_fields is not None:
@@ -252,7 +280,7 @@ class Colony:
         lat, n = self.lattice, self.n
         if lat is None or self.cells is not None or self.router is not None or n == 0:
             return
-        if self.motility is not None:
+        if self.motility is not None or self.mechanics is not None:
             return      # agents leave bin order every step: the separate launches
         if lat.pad_top or lat.pad_bot or not (lat.edge_top and lat.edge_bot):
             return
@@ -399,6 +427,8 @@ class Colony:
             stamp(0)
         if self.motility is not None:
             self._motility_step(dt)
+        if self.mechanics is not None:
+            self._mechanics_step()
         if self.lattice is not None and self.overlap_kinetics:
             # kinetics + gather read only the pre-step field and agent state, so
             # they run on a side stream beside the diffusion passes; the pass
@@ -483,6 +513,8 @@ class Colony:
             raise ValueError('growth and division run with step(): their derivers fix one clock')
         if self.motility is not None:
             raise ValueError('a motile colony steps with step(): the move runs on the step clock')
+        if self.mechanics is not None:
+            raise ValueError('a colony with mechanics steps with step(): the contacts run on the step clock')
         procs = [('diffusion', float(diffusion_dt)), ('kinetics', float(kinetics_dt))]   # store order
         front = {name: 0.0 for name, _ in procs}      # every update() call starts its fronts at 0
         pending = {}
@@ -573,10 +605,39 @@ class Colony:
             lat = self.lattice
             self._occ_dev.sort(self.bin_lin, self.n, lat.rows_local * lat.ny, getattr(self, 'agent_order', None))
 
+    def _mech_buffers(self):
+        """The device occupancy and the contact launch's scratch, counter and flag word
+        for ``ld`` agents (again when division grows ``ld``: the counter carries over)."""
+        gx, gy = self.mechanics.grid(self.lattice.bounds)
+        old = getattr(self, '_mech', None)
+        self._occ_dev = DeviceOccupancy(self.ld, self.device)
+        self._mech = ContactBuffers(self.ld, gx * gy, self.device)
+        if old is not None:
+            self._mech.counter.copy_(old.counter)
+            self._mech.flags.copy_(old.flags)
+
+    def _mechanics_step(self):
+        """First in the step of a colony with mechanics: the contact relaxation
+        (vk_contact_step; bins come out of it), then the device occupancy of the new
+        bins for the ordered exchange.  No host read and no re-layout: ``_layout``
+        stays, captured graphs stay valid."""
+        if self.router is not None:
+            raise ValueError('a colony with mechanics takes no router')
+        if self.cells is not None:
+            angle, length = self.cell[native.VK_CELL_ANGLE], self.cell[native.VK_CELL_LENGTH]
+        else:
+            angle, length = self.mech_angle, None
+        key = getattr(self, 'agent_order', None)
+        contact_step(self.mechanics, self.lattice, self.location, angle, self.n, self._mech, length=length,
+                     key=key, bin_lin=self.bin_lin, bin_ix=self.bin_ix)
+        if self.exchange_mode == 'sorted' and self.map_exch_count.numel():
+            lat = self.lattice
+            self._occ_dev.sort(self.bin_lin, self.n, lat.rows_local * lat.ny, key)
+
     def _step_exchange(self):
         lat = self.lattice
         if self.map_exch_count.numel():
-            if self.motility is not None and self.exchange_mode == 'sorted':
+            if (self.motility is not None or self.mechanics is not None) and self.exchange_mode == 'sorted':
                 lat.exchange_ordered(self._occ_dev.order, self._occ_dev.sorted_bin, self.n, self.counts,
                                      self.map_exch_count, self.map_exch_field)
             elif self.exchange_mode == 'sorted':
@@ -655,6 +716,7 @@ class Colony:
         re-binning of moved agents invalidates it (replay raises).  A motile
         colony (``motility=``) moves and re-bins its agents inside the graph:
         each replay continues the walk (the Philox counter lives on the device).
+        So does a colony with ``mechanics=`` and no cells.
         ``steps_per_launch`` > 1 (a held colony without division) captures
         :meth:`step_many` launches of that many steps instead.
         ``stamps`` (optional, a device int64 tensor of 3 * steps) records each
@@ -681,6 +743,8 @@ class Colony:
             self._step_buffers(spl)                 # allocated before the capture (graphs hold the pointers)
         if overlap and self.motility is not None:
             raise ValueError('Colony.capture: overlap is not available for a motile colony')
+        if overlap and self.mechanics is not None:
+            raise ValueError('Colony.capture: overlap is not available for a colony with mechanics')
         overlap = bool(overlap) and self._overlap_ok() and spl == 1
         if overlap and (getattr(self, '_counts_alt', None) is None or self._counts_alt.shape != self.counts.shape):
             self._counts_alt = torch.zeros_like(self.counts)
@@ -856,6 +920,8 @@ class Colony:
                 native.ptr(self.divide), n, native.ptr(src), native.ptr(kind), native.ptr(self._n_out),
                 native.ptr(scratch), native.stream_handle()), 'vk_divide_plan')
             n_out = int(self._n_out.item())
+            if self.mechanics is not None:
+                self._mech.check()       # the too-long flag, where the host reads anyway
         if self.router is not None:
             # collective every step: the global order of every rank's survivors
             # and daughters (AgentRouter.division_ordinals); then, if any rank
@@ -922,6 +988,8 @@ class Colony:
             self.ordinal = torch.zeros(ld, dtype=torch.int64, device=dev)
             self.ordinal[:n_out] = ordinal
         self.n, self.ld = n_out, ld
+        if self.mechanics is not None and ld != ld_src:
+            self._mech_buffers()
         if self.lattice is not None:
             self.bin_lin = torch.zeros(ld, dtype=torch.int32, device=dev)
             self.bin_ix = torch.zeros(ld, dtype=torch.int32, device=dev)
@@ -942,6 +1010,8 @@ class Colony:
         if bad.numel():
             a = int(bad[0])
             raise FloatingPointError('agent %d: kernel status %d' % (a, int(st[a])))
+        if self.mechanics is not None:
+            self._mech.check()
 
     # -- views ----------------------------------------------------------------------
     def species(self, port, name):
@@ -967,4 +1037,8 @@ class Colony:
         if self.motility is not None:
             m = self.motil[:, :self.n].cpu().numpy()
             out['motility'] = {name: m[row].copy() for row, name in enumerate(MOTIL_ROW_NAMES)}
+        if self.mechanics is not None:
+            angle = self.cell[native.VK_CELL_ANGLE] if self.cells is not None else self.mech_angle
+            out['mechanics'] = {'angle': angle[:self.n].cpu().numpy().copy(),
+                                'location': self.location[:, :self.n].cpu().numpy().copy()}
         return out

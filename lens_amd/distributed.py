@@ -151,6 +151,9 @@ class AgentRouter:
         if getattr(col, 'motility', None) is not None:
             raise ValueError('AgentRouter: a motile colony (Colony(motility=...)) takes no router: its agents '
                              'move and re-bin on one device, on a whole plane')
+        if getattr(col, 'mechanics', None) is not None:
+            raise ValueError('AgentRouter: a colony with mechanics (Colony(mechanics=...)) takes no router: its '
+                             'agents move and re-bin on one device, on a whole plane')
         lat = col.lattice
         bands = row_bands(lat.n_bins[0], world)
         if (lat.row_lo_global, lat.row_hi_global) != bands[rank]:

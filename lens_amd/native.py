@@ -32,7 +32,7 @@ EXPORTS = (
     'vk_exchange_atomic', 'vk_bin_sites', 'vk_cell_step', 'vk_divide_scratch_bytes', 'vk_divide_plan',
     'vk_divide_gather', 'vk_divide_lineage', 'vk_divide_locations', 'vk_kremling_step',
     'vk_expression_step', 'vk_motility_step', 'vk_occupancy_scratch_bytes', 'vk_occupancy_sort',
-    'vk_exchange_ordered',
+    'vk_exchange_ordered', 'vk_contact_scratch_bytes', 'vk_contact_step',
 )
 
 VK_CELL_MASS, VK_CELL_VOLUME, VK_CELL_LENGTH, VK_CELL_SURFACE_AREA, VK_CELL_PROTEIN, VK_CELL_ANGLE = range(6)
@@ -97,6 +97,12 @@ class VkMotilityParams(ctypes.Structure):
         'cw_to_ccw_leak', 'run_speed', 'tumble_sigma')] + [('seed', ctypes.c_uint64)]
 
 
+class VkContactParams(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('iterations', 'gx', 'gy', 'reserved')] + [
+        (n, ctypes.c_double) for n in ('stiffness', 'max_length', 'width', 'length', 'max_push', 'max_turn',
+                                       'jitter', 'jitter_angle')] + [('seed', ctypes.c_uint64)]
+
+
 _SIGS = {
     'vk_abi_version': ([], ctypes.c_int),
     'vk_last_error': ([], ctypes.c_char_p),
@@ -146,6 +152,9 @@ _SIGS = {
     'vk_occupancy_scratch_bytes': ([_i64], ctypes.c_int64),
     'vk_occupancy_sort': ([_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp], ctypes.c_int),
     'vk_exchange_ordered': ([_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _f64, _vp], ctypes.c_int),
+    'vk_contact_scratch_bytes': ([_i64, _i64], ctypes.c_int64),
+    'vk_contact_step': ([ctypes.POINTER(VkContactParams), _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32,
+                         _f64, _f64, _vp, _vp, _vp, _i64, _vp], ctypes.c_int),
 }
 
 _lib = None
