@@ -682,6 +682,91 @@ int vk_contact_step(const vk_contact_params *p, int64_t n_agents, int64_t ld, do
                     int32_t *bin_lin, int32_t *bin_ix, void *scratch, int64_t scratch_bytes,
                     vk_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Antibiotic response: membrane diffusion, death, the float exchange
+ *
+ *   vk_response_begin / vk_response_end (+ vk_response_cells)
+ *       stand, together with vk_expression_step, where the reference's
+ *       Antibiotics compartment (vivarium/compartments/antibiotics.py:106-159)
+ *       runs CellEnvironmentDiffusion.next_update (vivarium/processes/
+ *       diffusion_cell_environment.py:92-138) and DeathFreezeState.next_update
+ *       (vivarium/processes/death.py:105-118, 197-219) beside the kinetics.
+ *   vk_exchange_ordered_mixed / vk_exchange_atomic_f64
+ *       apply the membrane's float counts to the field with
+ *       update_field_with_exchange's conversion (vivarium/core/registry.py:
+ *       149-183), the first interleaved per agent with the kinetics' int64 counts.
+ *
+ * The existing launches (kinetics, expression, growth) run on every agent.  A
+ * frozen (dead) agent's columns are saved by `begin` and put back by `end`, so
+ * the launches' results for it are discarded and no launch changes.
+ * ------------------------------------------------------------------------- */
+
+/* All pointers are DEVICE arrays owned by the caller; rows index conc[][ld]. */
+typedef struct vk_response_table {
+    int32_t n_mol, n_porin, n_det, n_save, n_expr, n_flux, n_ext, reserved;
+    const int32_t *mol_int_row;   /* [n_mol] the cell's row of each diffusing molecule   */
+    const int32_t *mol_ext_row;   /* [n_mol] its ('external', m) row                      */
+    const int32_t *porin_row;     /* [n_porin]                                            */
+    const double *porin_perm;     /* [n_porin] permeability, summed in this order         */
+    const int32_t *det_row;       /* [n_det] detector keys                                */
+    const double *det_thr;        /* [n_det] dying when conc > thr (strict)               */
+    const int32_t *save_row;      /* [n_save] conc rows the kinetics launch overwrites    */
+    const int32_t *expr_row;      /* [n_expr] conc row of vk_expression_step's update row j */
+    double avogadro;              /* counts = flux_mmol * 1e-3 * avogadro                 */
+    double volume_fl;             /* every agent's volume (fL) when volume is NULL        */
+} vk_response_table;
+
+/* Before the kinetics launch, from the step-start state of agents [0, n):
+ *   dying[a] = !frozen[a] && any_d(conc[det_row[d]] > det_thr[d]);
+ *   rate = 0 + sum_p conc[porin_row[p]] * porin_perm[p] (in order);
+ *   flux_mmol = (conc[int_m] - conc[ext_m]) * rate * dt;
+ *   delta[m][a] = -(flux_mmol / volume * 1e15); fcounts[m][a] = flux_mmol * 1e-3 * avogadro;
+ *   frozen agents: save_conc[s][a] = conc[save_row[s]][a], save_flux := flux,
+ *   save_status := status, save_nsteps := nsteps.
+ * volume ([ld], fL; NULL: t->volume_fl).  flux is [n_flux][ld]; status and
+ * nsteps (and their save arrays) may be NULL.                                */
+int vk_response_begin(const vk_response_table *t, int64_t n_agents, int64_t ld, double dt, const double *conc,
+                      const double *volume, const int32_t *frozen, int32_t *dying, double *delta,
+                      double *fcounts, double *save_conc, const double *flux, double *save_flux,
+                      const int32_t *status, int32_t *save_status, const int32_t *nsteps,
+                      int32_t *save_nsteps, vk_stream_t stream);
+
+/* After the kinetics launch, before the exchange:
+ *   frozen agents: the saved columns go back and counts[e][a] = 0 (e < n_ext);
+ *   live agents: conc[expr_row[j]] += expr_update[j] (expr_update NULL: none);
+ *   every agent: conc[int_m] = conc[int_m] + delta[m];
+ *   dying agents: dead = frozen = 1.                                          */
+int vk_response_end(const vk_response_table *t, int64_t n_agents, int64_t ld, double *conc, const double *delta,
+                    const double *expr_update, int32_t *frozen, const int32_t *dying, int32_t *dead,
+                    const double *save_conc, double *flux, const double *save_flux, int32_t *status,
+                    const int32_t *save_status, int32_t *nsteps, const int32_t *save_nsteps,
+                    int64_t *counts, vk_stream_t stream);
+
+/* Around vk_cell_step: restore == 0 saves a frozen agent's cell rows
+ * ([VK_CELL_ROWS][ld]), mmol_to_counts and divide flag, restore != 0 puts them back.
+ * Agents with dying[a] != 0 (frozen by this step's vk_response_end) are left alone:
+ * the step of detection still grows and may divide them.                      */
+int vk_response_cells(int32_t restore, int64_t n_agents, int64_t ld, const int32_t *frozen,
+                      const int32_t *dying, double *cell, double *m2c, int32_t *divide, double *save_cell, double *save_m2c,
+                      int32_t *save_divide, vk_stream_t stream);
+
+/* vk_exchange_ordered with a second, float64 counts array and its own map.  Per
+ * bin, in segment (agent) order and per agent: v = v + mM(int count) then
+ * v = v + mM(float count), mM(c) = c / binvol_avogadro * 1000 -- what applying
+ * agent after agent gives.  Either array may be NULL (with its n_map 0).     */
+int vk_exchange_ordered_mixed(double *fields, int64_t field_stride, const int32_t *sorted_bin,
+                              const int32_t *order, int64_t n_agents, const int64_t *counts, int64_t ld,
+                              const int32_t *map_count, const int32_t *map_field, int32_t n_map,
+                              const double *fcounts, int64_t ld_f, const int32_t *map_fcount,
+                              const int32_t *map_ffield, int32_t n_fmap, double binvol_avogadro,
+                              vk_stream_t stream);
+
+/* vk_exchange_atomic for float64 counts (launched after the int64 one). */
+int vk_exchange_atomic_f64(double *fields, int64_t field_stride, const int32_t *bin_lin, int64_t n_agents,
+                           const double *fcounts, int64_t ld, const int32_t *map_count,
+                           const int32_t *map_field, int32_t n_map, double binvol_avogadro,
+                           vk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

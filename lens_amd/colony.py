@@ -32,6 +32,16 @@ multibody), and the bins and their occupancy are rebuilt on the device in the
 same way.  It combines with ``cells=``: growth and division then produce an
 expanding colony instead of a pile of overlapping daughters.
 
+With a :class:`~lens_amd.response.CellResponse` (``response=``) each agent is the
+reference's antibiotic-response cell: before the kinetics launch the death
+detector and the membrane's porin diffusion are evaluated from the step-start
+state and the pump's expression goes into an update buffer; after it the updates
+are applied in the compartment's process order (kinetics, expression, membrane
+last), dying agents are marked dead and frozen, and a frozen agent's kinetics,
+growth and expression results are discarded while its membrane keeps leaking.
+The exchange then adds each agent's int64 kinetic counts and its float membrane
+counts to the field, agent after agent.
+
 With a :class:`~lens_amd.cells.CellModel` the step continues like the
 reference's deriver pass: the growth process (from the step-start state),
 then TreeMass / DeriveGlobals (``mmol_to_counts`` for the next step's
@@ -55,6 +65,7 @@ from lens_amd.lattice import Lattice, occupancy, segment_index, N_A_LEGACY
 from lens_amd.mechanics import ContactBuffers, ContactModel, contact_step
 from lens_amd.motility import DeviceOccupancy, MotilityModel, ROW_NAMES as MOTIL_ROW_NAMES, motility_step
 from lens_amd.rate_law_compiler import compile_rate_laws, RateLawTable
+from lens_amd.response import CellResponse, ResponseBuffers, ResponseEngine
 
 
 def mmol_to_counts_from_mass(mass_fg, density_g_per_L=1100.0, avogadro=N_A_LEGACY):
@@ -69,7 +80,7 @@ class Colony:
                  avogadro: float = N_A_LEGACY, exchange: str = 'sorted', mass_fg: float = 1339.0,
                  table: Optional[RateLawTable] = None, specialize: bool = False,
                  cells: Optional[CellModel] = None, agent_ids=None, motility: Optional[MotilityModel] = None,
-                 mechanics: Optional[ContactModel] = None):
+                 mechanics: Optional[ContactModel] = None, response: Optional[CellResponse] = None):
         if integrator not in ('euler', 'dopri5'):
             raise ValueError('integrator must be euler or dopri5')
         if exchange not in ('sorted', 'atomic'):
@@ -100,6 +111,28 @@ class Colony:
                     mechanics.width, cells.width))
         self.config = config
         self.table = table or compile_rate_laws(config['reactions'], config['kinetic_parameters'])
+        self.response = response
+        self._resp_layout = None
+        if response is not None:
+            # checked before anything is built: the response needs a field to exchange with,
+            # and the agents stay where the contact launch or division puts them
+            if not isinstance(response, CellResponse):
+                raise ValueError('response must be a CellResponse')
+            if environment == 'held':
+                raise ValueError('response: a held environment has no field for the membrane to exchange with '
+                                 '(use nonspatial or a Lattice)')
+            if motility is not None:
+                raise ValueError('response with motility is not supported')
+            if isinstance(environment, Lattice):
+                if environment.pad_top or environment.pad_bot or not (environment.edge_top and environment.edge_bot):
+                    raise ValueError('response needs a whole, unbanded plane (row bands are not supported)')
+                for mol in (response.membrane or {}).get('molecules_to_diffuse', []):
+                    if mol not in environment.molecules:
+                        raise ValueError('response: the lattice has no %r plane for the membrane to exchange with '
+                                         '(molecules: %s)' % (mol, environment.molecules))
+            elif environment != 'nonspatial':
+                raise ValueError('environment must be held, nonspatial or a Lattice')
+            self._resp_layout = response.bind(self.table)     # ValueError: a key that resolves to no row
         self.device = native.resolve_device(device)
         # lattice colonies: optionally run kinetics + gather on a side stream
         # beside the diffusion passes (step()); results are identical either way.
@@ -135,7 +168,14 @@ class Colony:
         t, ld, dev = self.table, self.ld, self.device
         z = lambda *shape, dtype=torch.float64: torch.zeros(shape, dtype=dtype, device=dev)
         self.params = torch.from_numpy(np.repeat(t.param_defaults[:, None], ld, axis=1)).to(dev).contiguous()
-        self.conc = torch.from_numpy(initial_conc(t, config.get('initial_state', {}), ld)).to(dev).contiguous()
+        conc0 = initial_conc(t, config.get('initial_state', {}), ld)
+        if response is not None:
+            # the response's own rows follow the table's n_species rows
+            L = self._resp_layout
+            conc0 = np.concatenate([conc0, np.zeros((L.n_rows - t.n_species, ld))], axis=0)
+            for row, value in L.initial.items():
+                conc0[row, :] = value
+        self.conc = torch.from_numpy(conc0).to(dev).contiguous()
         self.m2c = torch.full((ld,), mmol_to_counts_from_mass(mass_fg, avogadro=avogadro),
                               dtype=torch.float64, device=dev)
         self.flux = z(t.n_reactions, ld)
@@ -154,6 +194,12 @@ class Colony:
         self.cells = cells
         self.motility = motility
         self.mechanics = mechanics
+        if response is not None:
+            self.dead = z(ld, dtype=torch.int32)
+            self.frozen = z(ld, dtype=torch.int32)
+            # DeriveGlobals' volume of mass_fg (fL), every agent's when there are no cells
+            volume_fl = CellModel(initial_mass=mass_fg).derive(mass_fg)[0]
+            self._resp = ResponseEngine(self._resp_layout, dev, avogadro, volume_fl, t.n_reactions, t.n_ext)
         if cells is not None:
             rows, m2c = cells.initial_rows(ld)
             self.cell = torch.from_numpy(rows).to(dev).contiguous()
@@ -186,7 +232,8 @@ class Colony:
                 self._mech_buffers()
         elif environment == 'nonspatial':
             mols = []
-            for e in t.external_ids + [k[1] for k in t.species if k[0] == 'external']:
+            extra = self._resp_layout.molecules if response is not None else []
+            for e in t.external_ids + [k[1] for k in t.species if k[0] == 'external'] + extra:
                 if e not in mols:
                     mols.append(e)
             self._setup_maps(mols)
@@ -199,6 +246,12 @@ class Colony:
             self._env_to_external()          # derivers run once at t = 0
         elif environment != 'held':
             raise ValueError('environment must be held, nonspatial or a Lattice')
+        if response is not None:
+            self._response_buffers()
+            if self.lattice is not None and exchange == 'sorted':
+                # the occupancy of the initial bins (set_agents(location=...) rebuilds it)
+                lat = self.lattice
+                self._occ_dev.sort(self.bin_lin, self.n, lat.rows_local * lat.ny, None)
 
     # -- maps between SoA rows and field planes ---------------------------------
     def _setup_maps(self, molecules):
@@ -214,12 +267,26 @@ class Colony:
                 xc.append(e)
                 xf.append(molecules.index(mol))
         i32 = lambda a: torch.tensor(a, dtype=torch.int32, device=self.device)
+        if self.response is not None:
+            # the membrane reads the agent's ('external', m) row and writes float counts
+            # into m's plane, whether or not a rate law mentions the molecule
+            L, fc, ff = self._resp_layout, [], []
+            for m, mol in enumerate(L.molecules):
+                f, row = molecules.index(mol), int(L.mol_ext_row[m])
+                if row not in gr:
+                    gf.append(f)
+                    gr.append(row)
+                fc.append(m)
+                ff.append(f)
+            self.map_fexch_count, self.map_fexch_field = i32(fc), i32(ff)
         self.map_gather_field, self.map_gather_row = i32(gf), i32(gr)
         self.map_exch_count, self.map_exch_field = i32(xc), i32(xf)
 
     # -- state I/O ----------------------------------------------------------------
-    def set_agents(self, params=None, conc=None, mmol_to_counts=None, location=None):
-        """Upload per-agent arrays ([rows, n] numpy or torch; columns 0..n-1)."""
+    def set_agents(self, params=None, conc=None, mmol_to_counts=None, location=None, environment=None):
+        """Upload per-agent arrays ([rows, n] numpy or torch; columns 0..n-1).
+        ``environment`` ([molecules, n], a nonspatial colony): each agent's own field,
+        copied into its external rows as the derivers do."""
         def put(dst, src):
             src = torch.as_tensor(src, dtype=dst.dtype)
             if src.dim() == 1:
@@ -232,6 +299,11 @@ class Colony:
             put(self.conc, conc)
         if mmol_to_counts is not None:
             put(self.m2c, mmol_to_counts)
+        if environment is not None:
+            if self.env_fields is None:
+                raise ValueError('environment values need a nonspatial colony')
+            put(self.env_fields, environment)
+            self._env_to_external()
         if location is not None:
             if self.lattice is None:
                 raise ValueError('locations need a lattice environment')
@@ -246,6 +318,8 @@ class Colony:
             names.append('location')
         if self.cells is not None:
             names += ['cell', 'divide', 'lin_root', 'lin_depth', 'lin_path']
+        if getattr(self, 'response', None) is not None:
+            names += ['dead', 'frozen']
         if getattr(self, 'motility', None) is not None:
             names.append('motil')
         if getattr(self, 'mechanics', None) is not None and self.cells is None:
@@ -269,6 +343,9 @@ class Colony:
             raise ValueError('agents outside this rank\'s row band: attach a distributed.AgentRouter '
                              '(division moves daughters across band edges)')
         self.occ = occupancy(self.bin_lin, self.n, getattr(self, 'agent_order', None))
+        if self.response is not None and self.exchange_mode == 'sorted':
+            # a response colony exchanges through the device occupancy: one ordered kernel
+            self._occ_dev.sort(self.bin_lin, self.n, lat.rows_local * lat.ny, getattr(self, 'agent_order', None))
         self._update_coupling()
         self._layout += 1            # captured graphs hold the old occupancy buffers
 
@@ -282,6 +359,8 @@ class Colony:
             return
         if self.motility is not None or self.mechanics is not None:
             return      # agents leave bin order every step: the separate launches
+        if self.response is not None:
+            return      # the mixed exchange is its own launch
         if lat.pad_top or lat.pad_bot or not (lat.edge_top and lat.edge_bot):
             return
         # stored in bin order, and within a bin in the exchange's agent order
@@ -334,6 +413,8 @@ class Colony:
                 t[:, :n] = t[:, :n][:, perm]
         self.agent_order = key[perm]
         self.occ = occupancy(self.bin_lin, n, self.agent_order)
+        if self.response is not None and self.exchange_mode == 'sorted':
+            self._occ_dev.sort(self.bin_lin, n, self.lattice.rows_local * self.lattice.ny, self.agent_order)
         self._update_coupling()
         self._layout += 1            # captured graphs hold the old occupancy buffers
         return self.agent_order
@@ -341,7 +422,7 @@ class Colony:
     def _gather_fused(self):
         """Whether this step's kinetics launch also does the gather."""
         return (self.fuse_gather and self.lattice is not None and self.integrator == 'dopri5' and
-                self.engine.default_variant() == 2 and 0 < self.map_gather_field.numel() <= 8)
+                self.response is None and self.engine.default_variant() == 2 and 0 < self.map_gather_field.numel() <= 8)
 
     def kinetics_and_gather(self, dt: float):
         """kinetics(dt) then gather_external(), as one launch when the kernel allows."""
@@ -376,12 +457,17 @@ class Colony:
         daughters (bench flop accounting)."""
         self.attempts = torch.zeros((), dtype=torch.int64, device=self.device) if on else None
 
+    def _kin_conc(self):
+        """The kinetics' view of ``conc``: the table's rows (a response colony keeps its
+        own rows after them, in the same allocation)."""
+        return self.conc if self.response is None else self.conc[:self.table.n_species]
+
     def kinetics(self, dt: float):
         if self.integrator == 'euler':
-            self.engine.euler(dt, self.params, self.conc, self.m2c, self.n, self.flux, self.counts,
+            self.engine.euler(dt, self.params, self._kin_conc(), self.m2c, self.n, self.flux, self.counts,
                               self.status)
         else:
-            self.engine.dopri5(dt, self.params, self.conc, self.m2c, self.n, self.h_state, self.rtol,
+            self.engine.dopri5(dt, self.params, self._kin_conc(), self.m2c, self.n, self.h_state, self.rtol,
                                self.atol, self.max_steps, self.flux, self.counts, self.status,
                                self.nsteps)
             if getattr(self, 'attempts', None) is not None:
@@ -403,6 +489,8 @@ class Colony:
         ``flux_steps`` [steps, R, ld], ``counts_steps`` [steps, E, ld] and
         ``nsteps_steps`` [steps, ld]; ``flux`` / ``counts`` / ``nsteps`` view
         the last step's."""
+        if self.response is not None:
+            raise ValueError('step_many: a colony with a response steps with step()')
         if self.environment != 'held' or self.cells is not None or self.integrator != 'dopri5':
             raise ValueError('step_many: held externals, no division, DP45 (agents must not couple between steps)')
         k = int(steps)
@@ -429,6 +517,13 @@ class Colony:
             self._motility_step(dt)
         if self.mechanics is not None:
             self._mechanics_step()
+        if self.response is not None:
+            if self.router is not None or halo_exchange is not None:
+                raise ValueError('a colony with a response takes no router and no row bands')
+            if self.overlap_kinetics or self.fuse_coupling:
+                raise ValueError('a colony with a response runs its launches in order on one stream '
+                                 '(overlap_kinetics and fuse_coupling are not available)')
+            self._response_begin(dt)
         if self.lattice is not None and self.overlap_kinetics:
             # kinetics + gather read only the pre-step field and agent state, so
             # they run on a side stream beside the diffusion passes; the pass
@@ -464,6 +559,8 @@ class Colony:
             self.kinetics_and_gather(dt)                     # + the pre-step field (one-step lag)
         else:
             self.kinetics(dt)
+        if self.response is not None:
+            self._response_end()
         if 'kin' in timing:
             timing['kin'][1].record()
         if stamp is not None:
@@ -485,6 +582,13 @@ class Colony:
                     native.ptr(self.counts), self.ld, native.ptr(self.map_exch_count),
                     native.ptr(self.map_exch_field), int(self.map_exch_count.numel()),
                     self.env_binvol_avogadro, native.stream_handle()), 'vk_exchange_atomic')
+            if self.response is not None and self.map_fexch_count.numel():
+                # each agent owns its bin: (field + int counts) + float counts, exactly
+                native.check(native._lib.vk_exchange_atomic_f64(
+                    native.ptr(self.env_fields), self.ld, native.ptr(self.env_bins), self.n,
+                    native.ptr(self._resp_buf.fcounts), self.ld, native.ptr(self.map_fexch_count),
+                    native.ptr(self.map_fexch_field), int(self.map_fexch_count.numel()),
+                    self.env_binvol_avogadro, native.stream_handle()), 'vk_exchange_atomic_f64')
             self._env_to_external()
         self._finish_step(dt)
         if stamp is not None:
@@ -515,6 +619,8 @@ class Colony:
             raise ValueError('a motile colony steps with step(): the move runs on the step clock')
         if self.mechanics is not None:
             raise ValueError('a colony with mechanics steps with step(): the contacts run on the step clock')
+        if self.response is not None:
+            raise ValueError('a colony with a response steps with step(): its processes share the step clock')
         procs = [('diffusion', float(diffusion_dt)), ('kinetics', float(kinetics_dt))]   # store order
         front = {name: 0.0 for name, _ in procs}      # every update() call starts its fronts at 0
         pending = {}
@@ -630,12 +736,45 @@ class Colony:
         key = getattr(self, 'agent_order', None)
         contact_step(self.mechanics, self.lattice, self.location, angle, self.n, self._mech, length=length,
                      key=key, bin_lin=self.bin_lin, bin_ix=self.bin_ix)
-        if self.exchange_mode == 'sorted' and self.map_exch_count.numel():
+        if self.exchange_mode == 'sorted' and (self.map_exch_count.numel() or self.response is not None):
             lat = self.lattice
             self._occ_dev.sort(self.bin_lin, self.n, lat.rows_local * lat.ny, key)
 
+    # -- the antibiotic response (lens_amd/response.py) ----------------------------
+    def _response_buffers(self):
+        """The response's per-agent scratch for ``ld`` agents, and the device occupancy of
+        the ordered exchange (again when division grows ``ld``)."""
+        self._resp_buf = ResponseBuffers(self._resp_layout, self.ld, self.table.n_reactions, self.device,
+                                         self.cells is not None)
+        if self.lattice is not None and self.mechanics is None:
+            self._occ_dev = DeviceOccupancy(self.ld, self.device)
+
+    def _response_begin(self, dt):
+        """Before the kinetics launch, all from the step-start state: the detector, the
+        membrane terms, the frozen agents' saved columns, the expression update."""
+        volume = self.cell[native.VK_CELL_VOLUME] if self.cells is not None else None
+        self._resp.begin(dt, self.n, self.conc, volume, self.frozen, self._resp_buf, self.flux, self.status,
+                         self.nsteps)
+
+    def _response_end(self):
+        """After the kinetics launch: frozen agents get their columns back, live ones the
+        expression update, every agent the membrane delta; dying agents freeze."""
+        self._resp.end(self.n, self.conc, self.frozen, self.dead, self._resp_buf, self.flux, self.status,
+                       self.nsteps, self.counts)
+
     def _step_exchange(self):
         lat = self.lattice
+        if self.response is not None:
+            fc = self._resp_buf.fcounts
+            if self.exchange_mode == 'sorted':
+                lat.exchange_ordered_mixed(self._occ_dev.order, self._occ_dev.sorted_bin, self.n, self.counts,
+                                           self.map_exch_count, self.map_exch_field, fc, self.map_fexch_count,
+                                           self.map_fexch_field)
+            else:
+                if self.map_exch_count.numel():
+                    lat.exchange_atomic(self.bin_lin, self.n, self.counts, self.map_exch_count, self.map_exch_field)
+                lat.exchange_atomic_f64(self.bin_lin, self.n, fc, self.map_fexch_count, self.map_fexch_field)
+            return
         if self.map_exch_count.numel():
             if (self.motility is not None or self.mechanics is not None) and self.exchange_mode == 'sorted':
                 lat.exchange_ordered(self._occ_dev.order, self._occ_dev.sorted_bin, self.n, self.counts,
@@ -739,12 +878,16 @@ class Colony:
         spl = int(steps_per_launch)
         if spl > 1 and (stamps is not None or steps % spl):
             raise ValueError('Colony.capture: steps_per_launch must divide steps (and takes no stamps)')
+        if spl > 1 and self.response is not None:
+            raise ValueError('Colony.capture: steps_per_launch is not available for a colony with a response')
         if spl > 1:
             self._step_buffers(spl)                 # allocated before the capture (graphs hold the pointers)
         if overlap and self.motility is not None:
             raise ValueError('Colony.capture: overlap is not available for a motile colony')
         if overlap and self.mechanics is not None:
             raise ValueError('Colony.capture: overlap is not available for a colony with mechanics')
+        if overlap and self.response is not None:
+            raise ValueError('Colony.capture: overlap is not available for a colony with a response')
         overlap = bool(overlap) and self._overlap_ok() and spl == 1
         if overlap and (getattr(self, '_counts_alt', None) is None or self._counts_alt.shape != self.counts.shape):
             self._counts_alt = torch.zeros_like(self.counts)
@@ -910,10 +1053,15 @@ class Colony:
             u = None
             if cm.model == 'growth_protein' and cm.rng == 'stream':
                 u = torch.from_numpy(cm.host_uniforms(n)).to(self.device)
+            if self.response is not None:
+                # an agent frozen before this step neither grows nor raises its division flag
+                self._resp.cells(False, n, self.frozen, self.cell, self.m2c, self.divide, self._resp_buf)
             native.check(native._lib.vk_cell_step(
                 ctypes.byref(p), n, self.ld, native.ptr(self.cell), native.ptr(self.m2c), native.ptr(u),
                 native.ptr(self.lin_root), native.ptr(self.lin_depth), native.ptr(self.lin_path),
                 native.ptr(self.divide), native.stream_handle()), 'vk_cell_step')
+            if self.response is not None:
+                self._resp.cells(True, n, self.frozen, self.cell, self.m2c, self.divide, self._resp_buf)
             scratch = torch.empty(int(native._lib.vk_divide_scratch_bytes(n)), dtype=torch.uint8,
                                   device=self.device)
             native.check(native._lib.vk_divide_plan(
@@ -970,6 +1118,11 @@ class Colony:
             cell.data_ptr() + n_split * ld * 8, ld, native.VK_CELL_ROWS - n_split, 8, S, st),
             'vk_divide_gather(angle)')
         self.divide = gather(self.divide, Z)
+        if self.response is not None:
+            # 'dead' has no divider (the set divider: both daughters inherit it); the
+            # daughters' processes are generated anew, so they are not frozen
+            self.dead = gather(self.dead)
+            self.frozen = gather(self.frozen, Z)
         root = torch.empty(ld, dtype=torch.int32, device=dev)
         depth = torch.empty(ld, dtype=torch.int32, device=dev)
         path = torch.empty(ld, dtype=torch.int64, device=dev)
@@ -990,6 +1143,8 @@ class Colony:
         self.n, self.ld = n_out, ld
         if self.mechanics is not None and ld != ld_src:
             self._mech_buffers()
+        if self.response is not None and ld != ld_src:
+            self._response_buffers()
         if self.lattice is not None:
             self.bin_lin = torch.zeros(ld, dtype=torch.int32, device=dev)
             self.bin_ix = torch.zeros(ld, dtype=torch.int32, device=dev)
@@ -1021,8 +1176,13 @@ class Colony:
         """Host copy of the emitted state ({port: {state: ndarray[n]}})."""
         out = {}
         c = self.conc[:, :self.n].cpu().numpy()
-        for s, (port, name) in enumerate(self.table.species):
+        keys = self.table.species if self.response is None else self._resp_layout.keys
+        for s, (port, name) in enumerate(keys):
             out.setdefault(port, {})[name] = c[s].copy()
+        if self.response is not None:
+            # counts deriver (derive_counts.py:42-51) on the expression's states, post-step
+            m2c = self.m2c[:self.n].cpu().numpy()
+            out['cell_counts'] = {keys[r][1]: np.trunc(c[r] * m2c) for r in self._resp_layout.expr_rows.tolist()}
         f = self.flux[:, :self.n].cpu().numpy()
         out['fluxes'] = {rid: f[r].copy() for r, rid in enumerate(self.table.reaction_ids)}
         if self.cells is not None:
@@ -1041,4 +1201,6 @@ class Colony:
             angle = self.cell[native.VK_CELL_ANGLE] if self.cells is not None else self.mech_angle
             out['mechanics'] = {'angle': angle[:self.n].cpu().numpy().copy(),
                                 'location': self.location[:, :self.n].cpu().numpy().copy()}
+        if self.response is not None:
+            out.setdefault('global', {})['dead'] = self.dead[:self.n].cpu().numpy().copy()
         return out

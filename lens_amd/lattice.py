@@ -425,6 +425,23 @@ class Lattice:
             native.ptr(counts), counts.shape[1], native.ptr(map_count), native.ptr(map_field),
             int(map_count.numel()), self.binvol_avogadro, native.stream_handle()), 'vk_exchange_ordered')
 
+    def exchange_ordered_mixed(self, order, sorted_bin, n_agents, counts, map_count, map_field, fcounts, map_fcount,
+                               map_ffield):
+        """:meth:`exchange_ordered` with float64 counts beside the int64 ones: per bin and
+        per agent, the int count and then the float count (vk_exchange_ordered_mixed)."""
+        native.check(native._lib.vk_exchange_ordered_mixed(
+            native.ptr(self.fields), self.field_stride, native.ptr(sorted_bin), native.ptr(order), n_agents,
+            native.ptr(counts), counts.shape[1], native.ptr(map_count), native.ptr(map_field),
+            int(map_count.numel()), native.ptr(fcounts), fcounts.shape[1], native.ptr(map_fcount),
+            native.ptr(map_ffield), int(map_fcount.numel()), self.binvol_avogadro, native.stream_handle()),
+            'vk_exchange_ordered_mixed')
+
+    def exchange_atomic_f64(self, bin_lin, n_agents, fcounts, map_count, map_field):
+        native.check(native._lib.vk_exchange_atomic_f64(
+            native.ptr(self.fields), self.field_stride, native.ptr(bin_lin), n_agents,
+            native.ptr(fcounts), fcounts.shape[1], native.ptr(map_count), native.ptr(map_field),
+            int(map_count.numel()), self.binvol_avogadro, native.stream_handle()), 'vk_exchange_atomic_f64')
+
     def exchange_atomic(self, bin_lin, n_agents, counts, map_count, map_field):
         native.check(native._lib.vk_exchange_atomic(
             native.ptr(self.fields), self.field_stride, native.ptr(bin_lin), n_agents,

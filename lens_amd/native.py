@@ -33,6 +33,8 @@ EXPORTS = (
     'vk_divide_gather', 'vk_divide_lineage', 'vk_divide_locations', 'vk_kremling_step',
     'vk_expression_step', 'vk_motility_step', 'vk_occupancy_scratch_bytes', 'vk_occupancy_sort',
     'vk_exchange_ordered', 'vk_contact_scratch_bytes', 'vk_contact_step',
+    'vk_response_begin', 'vk_response_end', 'vk_response_cells', 'vk_exchange_ordered_mixed',
+    'vk_exchange_atomic_f64',
 )
 
 VK_CELL_MASS, VK_CELL_VOLUME, VK_CELL_LENGTH, VK_CELL_SURFACE_AREA, VK_CELL_PROTEIN, VK_CELL_ANGLE = range(6)
@@ -103,6 +105,13 @@ class VkContactParams(ctypes.Structure):
                                        'jitter', 'jitter_angle')] + [('seed', ctypes.c_uint64)]
 
 
+class VkResponseTable(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('n_mol', 'n_porin', 'n_det', 'n_save', 'n_expr', 'n_flux', 'n_ext',
+                                              'reserved')] + [
+        (n, _vp) for n in ('mol_int_row', 'mol_ext_row', 'porin_row', 'porin_perm', 'det_row', 'det_thr',
+                           'save_row', 'expr_row')] + [('avogadro', ctypes.c_double), ('volume_fl', ctypes.c_double)]
+
+
 _SIGS = {
     'vk_abi_version': ([], ctypes.c_int),
     'vk_last_error': ([], ctypes.c_char_p),
@@ -155,6 +164,12 @@ _SIGS = {
     'vk_contact_scratch_bytes': ([_i64, _i64], ctypes.c_int64),
     'vk_contact_step': ([ctypes.POINTER(VkContactParams), _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32,
                          _f64, _f64, _vp, _vp, _vp, _i64, _vp], ctypes.c_int),
+    'vk_response_begin': ([ctypes.POINTER(VkResponseTable), _i64, _i64, _f64] + [_vp] * 14, ctypes.c_int),
+    'vk_response_end': ([ctypes.POINTER(VkResponseTable), _i64, _i64] + [_vp] * 15, ctypes.c_int),
+    'vk_response_cells': ([_i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+    'vk_exchange_ordered_mixed': ([_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _i32,
+                                   _f64, _vp], ctypes.c_int),
+    'vk_exchange_atomic_f64': ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _f64, _vp], ctypes.c_int),
 }
 
 _lib = None
