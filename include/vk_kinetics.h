@@ -35,7 +35,7 @@
  *   vk_bin_sites
  *       replaces get_bin_site (vivarium/library/lattice_utils.py:18-40).
  *   vk_cell_step / vk_divide_*, vk_kremling_step, vk_expression_step,
- *   vk_motility_step, vk_contact_step
+ *   vk_motility_step, vk_contact_step, vk_contact_step_channels, vk_population_plan
  *       are introduced by the comment blocks above their declarations.
  *
  * Conventions
@@ -376,6 +376,10 @@ int vk_bin_sites(const double *loc, int64_t n_agents, int64_t ld, int32_t nx, in
  *       with its dividers (core/registry.py:197-280): the new agent order is
  *       the survivors in order, then daughters id+'0', id+'1' of each mother
  *       in mother order; mothers are removed.
+ *   vk_population_plan
+ *       is vk_divide_plan with the `_delete` branch beside it (the mother
+ *       machine's outflow, multibody_physics.py:232-250): a removed agent gets
+ *       no slot, and a removed mother no daughters.
  * ------------------------------------------------------------------------- */
 
 /* Rows of the per-agent cell array cell[VK_CELL_ROWS][ld] ("global" port). */
@@ -442,6 +446,20 @@ int vk_cell_step(const vk_cell_params *p, int64_t n_agents, int64_t ld, double *
 int64_t vk_divide_scratch_bytes(int64_t n_agents);
 int vk_divide_plan(const int32_t *divide, int64_t n_agents, int32_t *src_index, int32_t *kind,
                    int64_t *n_out, void *scratch, vk_stream_t stream);
+
+/* Population plan: division and removal in one stable compaction, in the shape
+ * of vk_divide_plan's output (vk_divide_gather / _lineage / _locations take
+ * it).  Slots [0, n_keep): every agent with !remove && !divide, in agent order,
+ * kind -1; then two slots, kind 0 and 1, for every agent with divide &&
+ * !remove, in agent order.  A removed agent appears nowhere, whether or not it
+ * divides.  n_out = n - removed + kept mothers (may be < n, may be 0).  Either
+ * flag array may be NULL (all zero); with remove NULL the result is
+ * vk_divide_plan's bit for bit.  src_index and kind: n_out <= 2 n elements.
+ * scratch: >= vk_population_scratch_bytes(n).  No atomics, no host read.     */
+int64_t vk_population_scratch_bytes(int64_t n_agents);
+int vk_population_plan(const int32_t *divide, const int32_t *remove, int64_t n_agents,
+                       int32_t *src_index, int32_t *kind, int64_t *n_out, void *scratch,
+                       vk_stream_t stream);
 
 enum vk_divider {
     VK_DIVIDE_SET = 0,     /* both daughters copy the mother's value (no divider)  */
@@ -681,6 +699,53 @@ int vk_contact_step(const vk_contact_params *p, int64_t n_agents, int64_t ld, do
                     int32_t *flags, int32_t nx, int32_t ny, double bound_x, double bound_y,
                     int32_t *bin_lin, int32_t *bin_ix, void *scratch, int64_t scratch_bytes,
                     vk_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Mother machine: channel walls and outflow in the contact launch
+ *
+ *   vk_contact_step_channels
+ *       stands where the reference's multibody builds its mother machine
+ *       (vivarium/library/pymunk_multibody.py:218-230: vertical wall segments
+ *       at x = channel_space * line, 0 <= y <= channel_height, of thickness
+ *       spacer_thickness) and marks the cells pushed out of the top
+ *       (vivarium/processes/multibody_physics.py:232-250: y > channel_height
+ *       goes into `_delete`).  The wall law is THIS ENGINE'S OWN -- a
+ *       projection, not pymunk's segments -- and there is no flow.
+ *
+ * Lines stand at x = space * l, l = 0 .. n_lines - 1, n_lines = floor(bound_x /
+ * space); channel c lies between lines c and c + 1, the last one between line
+ * n_lines - 1 and the plane's edge.  After an agent's capped push and jitter,
+ * and before the plane's clamp:
+ *   y > height: the agent is left alone and outflow[a] is set (iteration 0
+ *     writes the flag, later iterations OR into it: an agent above the channels
+ *     after any iteration of the call stays flagged);
+ *   otherwise c = clamp(floor(x_snapshot / space), 0, n_lines - 1), the channel
+ *     the agent was in before the move, lo = c space + (r + spacer), hi =
+ *     (c + 1) space - (r + spacer) (the last channel: nextafter(bound_x, 0));
+ *     with h > 0 and |cos theta| > cmax = min((hi - lo) / (2 h), 1), theta :=
+ *     atan2(copysign(sqrt(1 - cmax^2), sin theta), copysign(cmax, cos theta));
+ *     then, e = h |cos theta|, x is clamped into [lo + e, max(hi - e, lo + e)].
+ * ------------------------------------------------------------------------- */
+
+typedef struct vk_contact_channels {
+    double height;                       /* um: 0 < height <= bound_y                  */
+    double space;                        /* um between lines, >= width + 2 spacer      */
+    double spacer;                       /* um: a line's thickness, >= 0               */
+    int32_t n_lines;                     /* floor(bound_x / space), >= 1               */
+    int32_t reserved;
+} vk_contact_channels;
+
+/* vk_contact_step with channels: the same arguments, then ch and outflow ([ld]
+ * int32, nullable: 1 for every agent of [0, n) above the channels after an
+ * iteration of this call, 0 for the others).  ch == NULL runs vk_contact_step
+ * itself (outflow is then not written).  Argument errors return VK_ERR_ARG and
+ * launch nothing.  No host synchronisation.                                  */
+int vk_contact_step_channels(const vk_contact_params *p, int64_t n_agents, int64_t ld,
+                             double *location, double *angle, const double *length,
+                             const int64_t *key, uint64_t *counter, int32_t *flags, int32_t nx,
+                             int32_t ny, double bound_x, double bound_y, int32_t *bin_lin,
+                             int32_t *bin_ix, void *scratch, int64_t scratch_bytes,
+                             const vk_contact_channels *ch, int32_t *outflow, vk_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Antibiotic response: membrane diffusion, death, the float exchange

@@ -32,6 +32,12 @@ multibody), and the bins and their occupancy are rebuilt on the device in the
 same way.  It combines with ``cells=``: growth and division then produce an
 expanding colony instead of a pile of overlapping daughters.
 
+A ContactModel with ``channels=`` makes the plane the reference's mother machine: the
+contact launch keeps every cell in its channel and flags the cells pushed out of
+the top, which take part in the step (their exchange lands) and leave at its end,
+in the same plan as division (vk_population_plan), or through :meth:`Colony.remove`
+when there are no cells.  ``remove(mask)`` takes agents out of any unrouted colony.
+
 With a :class:`~lens_amd.response.CellResponse` (``response=``) each agent is the
 reference's antibiotic-response cell: before the kinetics launch the death
 detector and the membrane's porin diffusion are evaluated from the step-start
@@ -109,6 +115,8 @@ class Colony:
             if cells is not None and float(cells.width) != mechanics.width:
                 raise ValueError('mechanics: the ContactModel\'s width (%r) must equal the CellModel\'s (%r)' % (
                     mechanics.width, cells.width))
+            if mechanics.channels is not None:
+                mechanics.check_channels(environment.bounds)     # ValueError: channels that do not fit the plane
         self.config = config
         self.table = table or compile_rate_laws(config['reactions'], config['kinetic_parameters'])
         self.response = response
@@ -718,6 +726,10 @@ class Colony:
         old = getattr(self, '_mech', None)
         self._occ_dev = DeviceOccupancy(self.ld, self.device)
         self._mech = ContactBuffers(self.ld, gx * gy, self.device)
+        if self.mechanics.channels is not None:
+            # the mother machine's outflow flags: written by every contact launch, read at
+            # the end of the step
+            self.outflow = torch.zeros(self.ld, dtype=torch.int32, device=self.device)
         if old is not None:
             self._mech.counter.copy_(old.counter)
             self._mech.flags.copy_(old.flags)
@@ -735,7 +747,8 @@ class Colony:
             angle, length = self.mech_angle, None
         key = getattr(self, 'agent_order', None)
         contact_step(self.mechanics, self.lattice, self.location, angle, self.n, self._mech, length=length,
-                     key=key, bin_lin=self.bin_lin, bin_ix=self.bin_ix)
+                     key=key, bin_lin=self.bin_lin, bin_ix=self.bin_ix,
+                     outflow=self.outflow if self.mechanics.channels is not None else None)
         if self.exchange_mode == 'sorted' and (self.map_exch_count.numel() or self.response is not None):
             lat = self.lattice
             self._occ_dev.sort(self.bin_lin, self.n, lat.rows_local * lat.ny, key)
@@ -868,6 +881,9 @@ class Colony:
         the last replayed step's counts.  Off by default: at C4 the overlapped kernels
         slow each other and each cross-stream dependency adds ~6 us, 1.518 against
         1.515 ms per step (profiles/r04/r04k)."""
+        if self._channels():
+            raise ValueError('Colony.capture: a colony with channels removes its outflow on the host every step '
+                             '(the agent count changes) and cannot be replayed from one graph')
         lat = self.lattice
         if (self.cells is not None or self.environment == 'nonspatial' or
                 (lat is not None and (lat.pad_top or lat.pad_bot or not (lat.edge_top and lat.edge_bot)))):
@@ -1023,6 +1039,8 @@ class Colony:
     def _finish_step(self, dt):
         if self.cells is not None:
             self.grow_and_divide(dt)
+        elif self._channels():
+            self.remove(self.outflow)    # the mother machine's outflow (with cells: planned with division)
         self.time += dt
         self.step_index += 1
 
@@ -1062,6 +1080,21 @@ class Colony:
                 native.ptr(self.divide), native.stream_handle()), 'vk_cell_step')
             if self.response is not None:
                 self._resp.cells(True, n, self.frozen, self.cell, self.m2c, self.divide, self._resp_buf)
+            if self._channels():
+                # the mother machine: the agents the contact launch flagged leave with this
+                # plan, and a flagged mother leaves no daughters.  Still one host read: the new
+                # count and the number removed together (equal counts can hide a removal)
+                scratch = torch.empty(int(native._lib.vk_population_scratch_bytes(n)), dtype=torch.uint8,
+                                      device=self.device)
+                native.check(native._lib.vk_population_plan(
+                    native.ptr(self.divide), native.ptr(self.outflow), n, native.ptr(src), native.ptr(kind),
+                    native.ptr(self._n_out), native.ptr(scratch), native.stream_handle()), 'vk_population_plan')
+                n_out, n_removed = torch.stack([self._n_out[0], (self.outflow[:n] != 0).sum()]).tolist()
+                self._mech.check()       # the too-long flag, where the host reads anyway
+                if n_out == n and n_removed == 0:
+                    return 0
+                self._apply_division(n_out, src, kind)
+                return n_out - n + n_removed
             scratch = torch.empty(int(native._lib.vk_divide_scratch_bytes(n)), dtype=torch.uint8,
                                   device=self.device)
             native.check(native._lib.vk_divide_plan(
@@ -1086,6 +1119,63 @@ class Colony:
             return 0
         self._apply_division(n_out, src, kind)
         return n_out - n
+
+    def _channels(self):
+        """Whether this colony is a mother machine (mechanics with channels)."""
+        return self.mechanics is not None and self.mechanics.channels is not None
+
+    def remove(self, mask):
+        """Take the agents a with ``mask[a] != 0`` out of the colony (``mask``: a device
+        int32 or bool tensor over agents [0, n)).  The others keep their order; every
+        per-agent array is gathered once into the same capacity (vk_population_plan with
+        no divide flags, then vk_divide_gather with the set divider), and bins and
+        occupancies are rebuilt as after a division.  Returns the number removed (one
+        host read).  ``col.remove(col.dead[:col.n] != 0)`` drops a response colony's dead."""
+        lat = self.lattice
+        if self.router is not None or (lat is not None and (
+                lat.pad_top or lat.pad_bot or not (lat.edge_top and lat.edge_bot))):
+            raise ValueError('Colony.remove: a colony with a router or a banded lattice keeps its agents '
+                             '(their global order lives on other ranks)')
+        n, ld, dev, st = self.n, self.ld, self.device, native.stream_handle()
+        if not torch.is_tensor(mask) or mask.device.type != dev.type or mask.dim() != 1 or mask.shape[0] < n or \
+                mask.dtype not in (torch.int32, torch.bool):
+            raise ValueError('Colony.remove: mask must be a device int32 or bool tensor over agents [0, n)')
+        if n == 0:
+            return 0
+        flags = mask[:n].to(torch.int32).contiguous()
+        src = torch.empty(n, dtype=torch.int32, device=dev)
+        kind = torch.empty(n, dtype=torch.int32, device=dev)
+        n_out_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+        scratch = torch.empty(int(native._lib.vk_population_scratch_bytes(n)), dtype=torch.uint8, device=dev)
+        native.check(native._lib.vk_population_plan(
+            0, native.ptr(flags), n, native.ptr(src), native.ptr(kind), native.ptr(n_out_dev), native.ptr(scratch),
+            st), 'vk_population_plan')
+        n_out = int(n_out_dev.item())
+        if n_out == n:
+            return 0
+        names = self.agent_array_names()
+        if getattr(self, 'agent_order', None) is not None:
+            names.append('agent_order')
+        for name in names:
+            t = getattr(self, name)
+            if not t.is_contiguous():        # flux / counts / nsteps may view step_many's buffers
+                t = t.contiguous()
+            rows = 1 if t.dim() == 1 else t.shape[0]
+            ld_src = t.shape[-1]
+            ld_dst = ld if ld_src == ld else n_out      # agent_order holds n keys, not ld
+            out = torch.zeros(t.shape[:-1] + (ld_dst,), dtype=t.dtype, device=dev)
+            native.check(native._lib.vk_divide_gather(
+                n_out, native.ptr(src), native.ptr(kind), native.ptr(t), ld_src, native.ptr(out), ld_dst, rows,
+                t.element_size(), native.VK_DIVIDE_SET, st), 'vk_divide_gather(%s)' % name)
+            setattr(self, name, out)
+        self.n = n_out
+        if lat is not None:
+            self.bin_lin = torch.zeros(ld, dtype=torch.int32, device=dev)
+            self.bin_ix = torch.zeros(ld, dtype=torch.int32, device=dev)
+            self.refresh_bins()          # bins, host and device occupancy, the _layout bump
+        else:
+            self._layout += 1
+        return n - n_out
 
     def _apply_division(self, n_out, src, kind, ordinal=None):
         ld_src = self.ld

@@ -232,5 +232,43 @@ def synthetic_network(n_species=50, n_reactions=40, n_enzymes=10, seed=SEED,
     return {'reactions': reactions, 'kinetic_parameters': kinetics, 'initial_state': initial}
 
 
+def mother_machine(n_agents=3, bounds=(20.0, 20.0), n_bins=(10, 10), channel_space=1.5, channel_height=None,
+                   spacer_thickness=0.1, seed=SEED):
+    """The reference's mother machine (vivarium/experiments/mother_machine.py):
+    get_mother_machine_config's values and mother_machine_body_config's placement --
+    one cell of length 2, width 1 and angle pi / 2 at the bottom (y = 0.01) of
+    ``n_agents`` of the channels, at ``x = k * space - space / 2``, k = 1 ..
+    n_spaces - 1, in shuffled order (a seeded NumPy permutation stands in for the
+    reference's ``random.shuffle``).  Returns a dict: ``bounds``, ``n_bins``,
+    ``channels`` (the ContactModel's ``channels=``), ``location`` [2, n], ``angle``
+    [n], ``length``, ``width``, ``volume`` (fL) and ``mass`` (fg at DeriveGlobals'
+    density of 1100 g/L: the CellModel's ``initial_mass``), ``growth_rate``,
+    ``division_volume``, ``jitter_force``, and the diffusion field's ``molecules``,
+    ``diffusion`` and ``gradient``."""
+    bounds = (float(bounds[0]), float(bounds[1]))
+    if channel_height is None:
+        channel_height = 0.7 * bounds[1]
+    n_spaces = math.floor(bounds[0] / channel_space)
+    if not n_agents < n_spaces:
+        raise ValueError('more agents than mother machine spaces')
+    width, length = 1.0, 2.0
+    radius = width / 2
+    # volume_from_length (vivarium/library/cell_geometry): the capsule's caps and cylinder
+    volume = (4 / 3) * math.pi * radius ** 3 + math.pi * radius ** 2 * (length - width)
+    possible = np.array([[k * channel_space - channel_space / 2, 0.01] for k in range(1, n_spaces)])
+    order = np.random.default_rng(seed).permutation(len(possible))
+    location = np.ascontiguousarray(possible[order[:n_agents]].T)
+    return {
+        'bounds': bounds, 'n_bins': tuple(n_bins),
+        'channels': {'channel_height': float(channel_height), 'channel_space': float(channel_space),
+                     'spacer_thickness': float(spacer_thickness)},
+        'location': location, 'angle': np.full(n_agents, math.pi / 2),
+        'length': length, 'width': width, 'volume': volume, 'mass': volume * 1100.0,
+        'growth_rate': 0.006, 'division_volume': 2.6, 'jitter_force': 1e-3,
+        'molecules': ['glc'], 'diffusion': 5e-3,
+        'gradient': {'type': 'gaussian', 'molecules': {'glc': {'center': [0.5, 0.5], 'deviation': 3}}},
+    }
+
+
 def deepcopy_config(cfg):
     return copy.deepcopy(cfg)

@@ -20,6 +20,8 @@
 // the agents dict, mother deleted).  The plan is one exclusive scan of the
 // divide flags (block counts -> one-block scan -> per-block ranks); every SoA
 // array is then gathered once into the new layout with its divider.
+// vk_population_plan is the same plan with removal (the mother machine's outflow,
+// multibody_physics.py:232-250 `_delete`; Colony.remove): a removed agent gets no slot.
 
 #include <stdint.h>
 
@@ -229,6 +231,187 @@ extern "C" int vk_divide_plan(const int32_t *divide, int64_t n, int32_t *src_ind
     if (nb > 0)
         hipLaunchKernelGGL(k_divide_place, dim3((unsigned)nb), dim3(256), 0, s, divide, n, bc, nb, src_index, kind);
     return vk::launch_check("vk_divide_plan");
+}
+
+// ---------------------------------------------------------------------------
+// population plan: division and removal in one stable compaction
+// ---------------------------------------------------------------------------
+//
+// The same three launches as the division plan, carrying two counts per block: the agents
+// removed and the mothers kept (divide && !remove).  An agent with R removed agents and M kept
+// mothers before it goes to slot a - R - M when it stays as it is, to n_keep + 2 M (and the
+// slot after) when it divides, nowhere when it is removed; n_keep = n - R_total - M_total.
+// scratch: removed[nb + 1] | mothers[nb + 1], int64 (the totals in element nb).
+
+extern "C" int64_t vk_population_scratch_bytes(int64_t n) {
+    if (n < 0) return 0;
+    const int64_t nb = (n + DV_BLOCK - 1) / DV_BLOCK;
+    return 2 * (nb + 2) * (int64_t)sizeof(int64_t);
+}
+
+__global__ __launch_bounds__(256) void k_population_count(const int32_t *__restrict__ divide,
+                                                          const int32_t *__restrict__ remove, int64_t n,
+                                                          int64_t *__restrict__ removed,
+                                                          int64_t *__restrict__ mothers) {
+    const int64_t base = (int64_t)blockIdx.x * DV_BLOCK;
+    int cr = 0, cm = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int64_t a = base + k * 256 + threadIdx.x;
+        if (a < n) {
+            const int r = remove ? (remove[a] != 0) : 0;
+            const int d = divide ? (divide[a] != 0) : 0;
+            cr += r;
+            cm += d & (r ^ 1);
+        }
+    }
+    __shared__ int part_r[4], part_m[4];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        cr += __shfl_xor(cr, o);
+        cm += __shfl_xor(cm, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        part_r[threadIdx.x >> 6] = cr;
+        part_m[threadIdx.x >> 6] = cm;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        removed[blockIdx.x] = part_r[0] + part_r[1] + part_r[2] + part_r[3];
+        mothers[blockIdx.x] = part_m[0] + part_m[1] + part_m[2] + part_m[3];
+    }
+}
+
+// one block: exclusive scans of both arrays of nb block counts in place; the totals go to
+// element nb of each, n - removed + mothers -> *n_out
+__global__ __launch_bounds__(256) void k_population_scan_blocks(int64_t *__restrict__ removed,
+                                                                int64_t *__restrict__ mothers, int64_t nb,
+                                                                int64_t n, int64_t *__restrict__ n_out) {
+    __shared__ int64_t carry[2];
+    __shared__ int64_t wsum[2][4];
+    if (threadIdx.x < 2) carry[threadIdx.x] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int64_t b0 = 0; b0 < nb; b0 += 256) {
+        const int64_t b = b0 + threadIdx.x;
+        const int64_t vr = b < nb ? removed[b] : 0, vm = b < nb ? mothers[b] : 0;
+        int64_t xr = vr, xm = vm;     // inclusive wave scans
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int64_t yr = __shfl_up(xr, o), ym = __shfl_up(xm, o);
+            if (lane >= o) {
+                xr += yr;
+                xm += ym;
+            }
+        }
+        if (lane == 63) {
+            wsum[0][w] = xr;
+            wsum[1][w] = xm;
+        }
+        __syncthreads();
+        int64_t wr = 0, wm = 0;
+        for (int k = 0; k < w; ++k) {
+            wr += wsum[0][k];
+            wm += wsum[1][k];
+        }
+        const int64_t er = carry[0] + wr + xr - vr, em = carry[1] + wm + xm - vm;
+        __syncthreads();
+        if (b < nb) {
+            removed[b] = er;
+            mothers[b] = em;
+        }
+        if (threadIdx.x == 255) {
+            carry[0] = er + vr;
+            carry[1] = em + vm;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        removed[nb] = carry[0];
+        mothers[nb] = carry[1];
+        *n_out = n - carry[0] + carry[1];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_population_place(const int32_t *__restrict__ divide,
+                                                          const int32_t *__restrict__ remove, int64_t n,
+                                                          const int64_t *__restrict__ removed_off,
+                                                          const int64_t *__restrict__ mothers_off, int64_t nb,
+                                                          int32_t *__restrict__ src_index,
+                                                          int32_t *__restrict__ kind) {
+    const int64_t base = (int64_t)blockIdx.x * DV_BLOCK;
+    const int64_t n_keep = n - removed_off[nb] - mothers_off[nb];
+    __shared__ int wcount[2][4];
+    // per-thread 4 consecutive agents -> thread-level counts -> block exclusive scans
+    const int64_t a0 = base + (int64_t)threadIdx.x * 4;
+    int fr[4], fm[4], cr = 0, cm = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        fr[k] = (a0 + k < n && remove) ? (remove[a0 + k] != 0) : 0;
+        fm[k] = (a0 + k < n && divide) ? ((divide[a0 + k] != 0) & (fr[k] ^ 1)) : 0;
+        cr += fr[k];
+        cm += fm[k];
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int xr = cr, xm = cm;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int yr = __shfl_up(xr, o), ym = __shfl_up(xm, o);
+        if (lane >= o) {
+            xr += yr;
+            xm += ym;
+        }
+    }
+    if (lane == 63) {
+        wcount[0][w] = xr;
+        wcount[1][w] = xm;
+    }
+    __syncthreads();
+    int wr = 0, wm = 0;
+    for (int k = 0; k < w; ++k) {
+        wr += wcount[0][k];
+        wm += wcount[1][k];
+    }
+    int64_t r = removed_off[blockIdx.x] + wr + xr - cr;   // removed before a0
+    int64_t m = mothers_off[blockIdx.x] + wm + xm - cm;   // kept mothers before a0
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int64_t a = a0 + k;
+        if (a >= n) break;
+        if (fr[k]) {
+            ++r;
+        } else if (fm[k]) {
+            const int64_t j = n_keep + 2 * m;     // < n_out <= 2 n
+            src_index[j] = (int32_t)a;
+            kind[j] = 0;
+            src_index[j + 1] = (int32_t)a;
+            kind[j + 1] = 1;
+            ++m;
+        } else {
+            const int64_t j = a - r - m;          // >= 0: r + m counts agents before a
+            src_index[j] = (int32_t)a;
+            kind[j] = -1;
+        }
+    }
+}
+
+extern "C" int vk_population_plan(const int32_t *divide, const int32_t *remove, int64_t n, int32_t *src_index,
+                                  int32_t *kind, int64_t *n_out, void *scratch, vk_stream_t stream) {
+    if (n < 0 || n > 0x3fffffff || !n_out || !scratch || (n > 0 && (!src_index || !kind))) {
+        vk::set_error("vk_population_plan: bad arguments");
+        return VK_ERR_ARG;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t nb = (n + DV_BLOCK - 1) / DV_BLOCK;
+    int64_t *removed = (int64_t *)scratch, *mothers = removed + nb + 2;
+    if (nb > 0)
+        hipLaunchKernelGGL(k_population_count, dim3((unsigned)nb), dim3(256), 0, s, divide, remove, n, removed,
+                           mothers);
+    hipLaunchKernelGGL(k_population_scan_blocks, dim3(1), dim3(256), 0, s, removed, mothers, nb, n, n_out);
+    if (nb > 0)
+        hipLaunchKernelGGL(k_population_place, dim3((unsigned)nb), dim3(256), 0, s, divide, remove, n, removed,
+                           mothers, nb, src_index, kind);
+    return vk::launch_check("vk_population_plan");
 }
 
 // ---------------------------------------------------------------------------

@@ -34,6 +34,14 @@
 //                     agent's own column; `packed` is the snapshot, so the write is in place.
 // The last iteration also writes bin_lin / bin_ix with vk_bin_sites' arithmetic.
 //
+// Channels (vk_contact_step_channels, the reference's mother machine: pymunk_multibody.py:
+// 218-230, multibody_physics.py:232-250): vertical lines at x = space * l, l < n_lines, from the
+// floor to `height`.  k_contact_relax<true> projects each agent after its push and jitter and
+// before the plane's clamp -- an agent above `height` is left alone and flagged in outflow[],
+// any other is turned until its spine fits its channel and its centre is clamped between the
+// lines -- a closed form per agent: no loop over lines, no LDS, nothing shared.  This too is
+// the engine's own law, not pymunk's segments.  k_contact_relax<false> is the kernel without.
+//
 // Hazards: no kernel waits on another workgroup, nothing is polled, every loop is bounded by
 // cell_end - cell_start, and the only atomic is the atomicOr on the flag word.
 //
@@ -115,12 +123,16 @@ __global__ __launch_bounds__(256) void k_contact_pack(int n, int64_t ld, const d
 
 __device__ __forceinline__ double clampd(double v, double lo, double hi) { return fmin(fmax(v, lo), hi); }
 
+// CH: the mother machine's channel walls and outflow flag (vk_contact_step_channels); the
+// instantiation without them is the kernel as it was.
+template <bool CH>
 __global__ __launch_bounds__(256) void k_contact_relax(
     vk_contact_params p, int n, int64_t ld, const contact_slot *__restrict__ packed, const double2 *__restrict__ dir,
     const uint32_t *__restrict__ skey, const int32_t *__restrict__ order, const int32_t *__restrict__ sorted_cell,
     const int32_t *__restrict__ cell_start, const int32_t *__restrict__ cell_end, const uint64_t *__restrict__ counter,
     int iteration, double bx_below, double by_below, double *__restrict__ loc, double *__restrict__ angle, int nx,
-    int ny, double bx, double by, int32_t *__restrict__ bin_lin, int32_t *__restrict__ bin_ix) {
+    int ny, double bx, double by, int32_t *__restrict__ bin_lin, int32_t *__restrict__ bin_ix,
+    vk_contact_channels ch, int32_t *__restrict__ outflow) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
     const contact_slot me = packed[k];
@@ -230,9 +242,39 @@ __global__ __launch_bounds__(256) void k_contact_relax(
         y += p.jitter * (r0 * sin(6.283185307179586 * u1));
         th += p.jitter_angle * (r1 * cos(6.283185307179586 * u3));
     }
+    const int a = order[k];
+    if constexpr (CH) {
+        // The channel walls: a projection, after the push and the jitter.  An agent above the
+        // channels is left alone and flagged (iteration 0 writes the flag, later ones OR into
+        // it).  Any other stays in the channel its snapshot centre was in: its axis is turned
+        // until the spine fits between the two lines, then the centre is clamped so that both
+        // spine ends keep r + spacer from them.  Right of the last line the plane's edge stands in.
+        const bool out = y > ch.height;
+        if (outflow) {
+            if (iteration == 0) outflow[a] = out ? 1 : 0;
+            else if (out) outflow[a] = 1;
+        }
+        if (!out) {
+            const double cf = floor(me.x / ch.space);
+            const int c = !(cf >= 0.0) ? 0 : (cf < (double)ch.n_lines ? (int)cf : ch.n_lines - 1);
+            const double wl = (double)c * ch.space + (r + ch.spacer);
+            const double wh = c + 1 < ch.n_lines ? (double)(c + 1) * ch.space - (r + ch.spacer) : bx_below;
+            double ac = 0.0;      // |cos theta| of the angle the agent ends with
+            if (hi > 0.0) {
+                const double cs = cos(th), sn = sin(th);
+                const double cmax = fmin((wh - wl) / (2.0 * hi), 1.0);
+                ac = fabs(cs);
+                if (ac > cmax) {
+                    th = atan2(copysign(sqrt(1.0 - cmax * cmax), sn), copysign(cmax, cs));
+                    ac = cmax;
+                }
+            }
+            const double e = hi * ac;
+            x = fmin(fmax(x, wl + e), fmax(wh - e, wl + e));
+        }
+    }
     x = fmin(fmax(x, 0.0), bx_below);
     y = fmin(fmax(y, 0.0), by_below);
-    const int a = order[k];
     loc[a] = x;
     loc[ld + a] = y;
     angle[a] = th;
@@ -248,10 +290,10 @@ __global__ void k_contact_advance(uint64_t *counter, uint64_t by) {
     if (blockIdx.x == 0 && threadIdx.x == 0) counter[0] += by;
 }
 
-extern "C" int vk_contact_step(const vk_contact_params *p, int64_t n, int64_t ld, double *location, double *angle,
-                               const double *length, const int64_t *key, uint64_t *counter, int32_t *flags,
-                               int32_t nx, int32_t ny, double bound_x, double bound_y, int32_t *bin_lin,
-                               int32_t *bin_ix, void *scratch, int64_t scratch_bytes, vk_stream_t stream) {
+static int contact_step(const vk_contact_params *p, int64_t n, int64_t ld, double *location, double *angle,
+                        const double *length, const int64_t *key, uint64_t *counter, int32_t *flags, int32_t nx,
+                        int32_t ny, double bound_x, double bound_y, int32_t *bin_lin, int32_t *bin_ix, void *scratch,
+                        int64_t scratch_bytes, vk_stream_t stream, const vk_contact_channels *ch, int32_t *outflow) {
     if (!p || n < 0 || n >= INT32_MAX || ld < n || !counter || !flags || nx <= 0 || ny <= 0 || !(bound_x > 0.0) ||
         !(bound_y > 0.0) || (int64_t)nx * ny >= INT32_MAX) {
         vk::set_error("vk_contact_step: bad arguments");
@@ -269,6 +311,13 @@ extern "C" int vk_contact_step(const vk_contact_params *p, int64_t n, int64_t ld
         (p->gx > 1 && bound_x / p->gx < p->max_length) || (p->gy > 1 && bound_y / p->gy < p->max_length)) {
         vk::set_error("vk_contact_step: the grid must be gx = max(1, floor(bound_x / max_length)) by gy likewise "
                       "(cell edges >= max_length)");
+        return VK_ERR_ARG;
+    }
+    if (ch && (!(ch->height > 0.0) || !(ch->height <= bound_y) || !(ch->spacer >= 0.0) ||
+               !(ch->space >= p->width + 2.0 * ch->spacer) || ch->n_lines < 1 ||
+               (double)ch->n_lines != floor(bound_x / ch->space))) {
+        vk::set_error("vk_contact_step_channels: 0 < height <= bound_y, spacer >= 0, space >= width + 2 spacer, "
+                      "n_lines = floor(bound_x / space) >= 1");
         return VK_ERR_ARG;
     }
     if (n == 0) return VK_OK;
@@ -311,12 +360,37 @@ extern "C" int vk_contact_step(const vk_contact_params *p, int64_t n, int64_t ld
                            order, sorted_cell, packed, dir, skey, cell_start, cell_end);
         rc = vk::launch_check("k_contact_pack");
         if (rc) return rc;
-        hipLaunchKernelGGL(k_contact_relax, grid, block, 0, s, *p, (int)n, ld, packed, dir, skey, order, sorted_cell,
-                           cell_start, cell_end, counter, it, bx_below, by_below, location, angle, nx, ny, bound_x,
-                           bound_y, last ? bin_lin : (int32_t *)nullptr, last ? bin_ix : (int32_t *)nullptr);
+        if (ch)
+            hipLaunchKernelGGL(k_contact_relax<true>, grid, block, 0, s, *p, (int)n, ld, packed, dir, skey, order,
+                               sorted_cell, cell_start, cell_end, counter, it, bx_below, by_below, location, angle, nx,
+                               ny, bound_x, bound_y, last ? bin_lin : (int32_t *)nullptr,
+                               last ? bin_ix : (int32_t *)nullptr, *ch, outflow);
+        else
+            hipLaunchKernelGGL(k_contact_relax<false>, grid, block, 0, s, *p, (int)n, ld, packed, dir, skey, order,
+                               sorted_cell, cell_start, cell_end, counter, it, bx_below, by_below, location, angle, nx,
+                               ny, bound_x, bound_y, last ? bin_lin : (int32_t *)nullptr,
+                               last ? bin_ix : (int32_t *)nullptr, vk_contact_channels{}, (int32_t *)nullptr);
         rc = vk::launch_check("k_contact_relax");
         if (rc) return rc;
     }
     hipLaunchKernelGGL(k_contact_advance, dim3(1), dim3(64), 0, s, counter, (uint64_t)p->iterations);
     return vk::launch_check("k_contact_advance");
+}
+
+extern "C" int vk_contact_step(const vk_contact_params *p, int64_t n, int64_t ld, double *location, double *angle,
+                               const double *length, const int64_t *key, uint64_t *counter, int32_t *flags,
+                               int32_t nx, int32_t ny, double bound_x, double bound_y, int32_t *bin_lin,
+                               int32_t *bin_ix, void *scratch, int64_t scratch_bytes, vk_stream_t stream) {
+    return contact_step(p, n, ld, location, angle, length, key, counter, flags, nx, ny, bound_x, bound_y, bin_lin,
+                        bin_ix, scratch, scratch_bytes, stream, nullptr, nullptr);
+}
+
+// vk_contact_step with the mother machine's channels; ch == NULL runs vk_contact_step's own code
+extern "C" int vk_contact_step_channels(const vk_contact_params *p, int64_t n, int64_t ld, double *location,
+                                        double *angle, const double *length, const int64_t *key, uint64_t *counter,
+                                        int32_t *flags, int32_t nx, int32_t ny, double bound_x, double bound_y,
+                                        int32_t *bin_lin, int32_t *bin_ix, void *scratch, int64_t scratch_bytes,
+                                        const vk_contact_channels *ch, int32_t *outflow, vk_stream_t stream) {
+    return contact_step(p, n, ld, location, angle, length, key, counter, flags, nx, ny, bound_x, bound_y, bin_lin,
+                        bin_ix, scratch, scratch_bytes, stream, ch, ch ? outflow : nullptr);
 }

@@ -23,6 +23,15 @@ re-bins its agents on the device, as a motile colony does.  With ``cells=`` a
 capsule's length is the agent's ``VK_CELL_LENGTH`` row and its angle the
 ``VK_CELL_ANGLE`` row; without, every agent has ``length`` and the colony owns
 a ``mech_angle`` array.
+
+``channels=`` turns the plane into the reference's mother machine
+(vivarium/library/pymunk_multibody.py:218-230, multibody_physics.py:232-250):
+vertical lines at ``x = channel_space * l``, ``l = 0 .. n_lines - 1``, from the
+floor up to ``channel_height``, of thickness ``spacer_thickness``.  The launch
+(vk_contact_step_channels) keeps every agent below ``channel_height`` in the
+channel it is in -- a projection of its angle and centre, this engine's own wall
+law, no pymunk segments and no flow -- and flags the agents above it, which the
+colony removes at the end of the step.
 """
 
 from __future__ import annotations
@@ -36,12 +45,13 @@ import numpy as np
 from lens_amd import native
 
 TOO_LONG = 1      # bit 0 of the flag word
+CHANNEL_KEYS = ('channel_height', 'channel_space', 'spacer_thickness')
 
 
 class ContactModel:
     def __init__(self, iterations: int = 4, stiffness: float = 0.5, max_length: float = 4.0, width: float = 1.0,
                  length: float = 2.0, max_push: Optional[float] = None, max_turn: float = 0.5, jitter: float = 0.0,
-                 jitter_angle: float = 0.0, seed: int = 0, angles=None, **unknown):
+                 jitter_angle: float = 0.0, seed: int = 0, angles=None, channels=None, **unknown):
         if unknown:
             raise ValueError('unknown ContactModel parameters: %s' % sorted(unknown))
         if int(iterations) != iterations or int(iterations) < 1:
@@ -70,6 +80,26 @@ class ContactModel:
         self.jitter, self.jitter_angle = float(jitter), float(jitter_angle)
         self.seed = int(seed)
         self.angles = angles                 # initial axis angles (rad) per agent; None: seeded uniform
+        self.channels = None
+        if channels is not None:
+            # the reference's multibody keys (its 'mother_machine' dictionary)
+            ch = dict(channels)
+            bad = sorted(set(ch) - set(CHANNEL_KEYS))
+            if bad:
+                raise ValueError('unknown channels keys: %s (known: %s)' % (bad, list(CHANNEL_KEYS)))
+            for k in ('channel_height', 'channel_space'):
+                if k not in ch:
+                    raise ValueError('channels needs %r' % k)
+            ch.setdefault('spacer_thickness', 0.1)
+            ch = {k: float(ch[k]) for k in CHANNEL_KEYS}
+            if not ch['channel_height'] > 0.0:
+                raise ValueError('channels: channel_height must be positive')
+            if not ch['spacer_thickness'] >= 0.0:
+                raise ValueError('channels: spacer_thickness must be >= 0')
+            if not ch['channel_space'] >= self.width + 2.0 * ch['spacer_thickness']:
+                raise ValueError('channels: channel_space must be at least width + 2 * spacer_thickness '
+                                 '(a cell must fit between two lines)')
+            self.channels = ch
 
     def grid(self, bounds):
         """(gx, gy): the neighbour grid on ``bounds``, cell edges >= max_length."""
@@ -98,6 +128,30 @@ class ContactModel:
         p.seed = self.seed & (2 ** 64 - 1)
         return p
 
+    def n_lines(self, bounds) -> int:
+        """floor(bound_x / channel_space): the reference's count of wall lines."""
+        return int(math.floor(float(bounds[0]) / self.channels['channel_space']))
+
+    def check_channels(self, bounds):
+        """The channels against a plane of ``bounds``: raises ValueError."""
+        ch = self.channels
+        if not ch['channel_height'] <= float(bounds[1]):
+            raise ValueError('channels: channel_height (%r) must not exceed bound_y (%r)' % (
+                ch['channel_height'], float(bounds[1])))
+        if self.n_lines(bounds) < 1:
+            raise ValueError('channels: channel_space (%r) leaves no line on bound_x (%r)' % (
+                ch['channel_space'], float(bounds[0])))
+
+    def vk_channels(self, bounds) -> Optional[native.VkContactChannels]:
+        if self.channels is None:
+            return None
+        self.check_channels(bounds)
+        c = native.VkContactChannels()
+        c.height, c.space = self.channels['channel_height'], self.channels['channel_space']
+        c.spacer = self.channels['spacer_thickness']
+        c.n_lines = self.n_lines(bounds)
+        return c
+
 
 class ContactBuffers:
     """What vk_contact_step needs beside the agents, for up to ``ld`` agents on
@@ -123,12 +177,15 @@ class ContactBuffers:
 
 
 def contact_step(model: ContactModel, lattice, location, angle, n: int, buffers: ContactBuffers, length=None,
-                 key=None, bin_lin=None, bin_ix=None):
+                 key=None, bin_lin=None, bin_ix=None, outflow=None):
     """One vk_contact_step launch sequence on the current stream:
     ``model.iterations`` relaxation iterations for agents [0, n) of ``location``
     [2, ld] and ``angle`` [ld] (both updated in place); ``length`` [ld] or None
     for the model's constant.  ``bin_lin`` / ``bin_ix`` (int32 [ld]) receive the
-    bins.  The lattice must hold whole, unbanded planes.  No host read."""
+    bins.  A model with channels goes through vk_contact_step_channels, and
+    ``outflow`` (int32 [ld], optional) receives 1 for every agent above the channels
+    after an iteration, 0 for the others.  The lattice must hold whole, unbanded
+    planes.  No host read."""
     import torch
     if lattice.pad_top or lattice.pad_bot or not (lattice.edge_top and lattice.edge_bot):
         raise ValueError('contact_step: a whole, unbanded plane')
@@ -143,6 +200,20 @@ def contact_step(model: ContactModel, lattice, location, angle, n: int, buffers:
         raise ValueError('contact_step: the buffers were sized for fewer agents or another grid')
     if bin_lin is None:
         bin_lin = torch.zeros(ld, dtype=torch.int32, device=location.device)
+    ch = model.vk_channels(lattice.bounds)
+    if ch is not None:
+        if outflow is not None and not (outflow.dtype == torch.int32 and outflow.dim() == 1 and
+                                        outflow.shape[0] >= ld and outflow.stride(0) == 1):
+            raise ValueError('contact_step: outflow must be an int32 row of ld elements')
+        native.check(native._lib.vk_contact_step_channels(
+            ctypes.byref(p), n, ld, native.ptr(location), native.ptr(angle), native.ptr(length), native.ptr(key),
+            native.ptr(buffers.counter), native.ptr(buffers.flags), lattice.n_bins[0], lattice.n_bins[1],
+            lattice.bounds[0], lattice.bounds[1], native.ptr(bin_lin), native.ptr(bin_ix),
+            buffers.scratch.data_ptr() + buffers._off, buffers._bytes, ctypes.byref(ch), native.ptr(outflow),
+            native.stream_handle()), 'vk_contact_step_channels')
+        return bin_lin
+    if outflow is not None:
+        raise ValueError('contact_step: outflow needs a model with channels')
     native.check(native._lib.vk_contact_step(
         ctypes.byref(p), n, ld, native.ptr(location), native.ptr(angle), native.ptr(length), native.ptr(key),
         native.ptr(buffers.counter), native.ptr(buffers.flags), lattice.n_bins[0], lattice.n_bins[1],

@@ -34,7 +34,7 @@ EXPORTS = (
     'vk_expression_step', 'vk_motility_step', 'vk_occupancy_scratch_bytes', 'vk_occupancy_sort',
     'vk_exchange_ordered', 'vk_contact_scratch_bytes', 'vk_contact_step',
     'vk_response_begin', 'vk_response_end', 'vk_response_cells', 'vk_exchange_ordered_mixed',
-    'vk_exchange_atomic_f64',
+    'vk_exchange_atomic_f64', 'vk_population_scratch_bytes', 'vk_population_plan', 'vk_contact_step_channels',
 )
 
 VK_CELL_MASS, VK_CELL_VOLUME, VK_CELL_LENGTH, VK_CELL_SURFACE_AREA, VK_CELL_PROTEIN, VK_CELL_ANGLE = range(6)
@@ -105,6 +105,11 @@ class VkContactParams(ctypes.Structure):
                                        'jitter', 'jitter_angle')] + [('seed', ctypes.c_uint64)]
 
 
+class VkContactChannels(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_double) for n in ('height', 'space', 'spacer')] + [
+        ('n_lines', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
 class VkResponseTable(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ('n_mol', 'n_porin', 'n_det', 'n_save', 'n_expr', 'n_flux', 'n_ext',
                                               'reserved')] + [
@@ -164,6 +169,11 @@ _SIGS = {
     'vk_contact_scratch_bytes': ([_i64, _i64], ctypes.c_int64),
     'vk_contact_step': ([ctypes.POINTER(VkContactParams), _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32,
                          _f64, _f64, _vp, _vp, _vp, _i64, _vp], ctypes.c_int),
+    'vk_contact_step_channels': ([ctypes.POINTER(VkContactParams), _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32,
+                                  _i32, _f64, _f64, _vp, _vp, _vp, _i64, ctypes.POINTER(VkContactChannels), _vp, _vp],
+                                 ctypes.c_int),
+    'vk_population_scratch_bytes': ([_i64], ctypes.c_int64),
+    'vk_population_plan': ([_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     'vk_response_begin': ([ctypes.POINTER(VkResponseTable), _i64, _i64, _f64] + [_vp] * 14, ctypes.c_int),
     'vk_response_end': ([ctypes.POINTER(VkResponseTable), _i64, _i64] + [_vp] * 15, ctypes.c_int),
     'vk_response_cells': ([_i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
