@@ -35,7 +35,7 @@
  *   vk_bin_sites
  *       replaces get_bin_site (vivarium/library/lattice_utils.py:18-40).
  *   vk_cell_step / vk_divide_*, vk_kremling_step, vk_expression_step,
- *   vk_motility_step, vk_contact_step, vk_contact_step_channels, vk_population_plan
+ *   vk_motility_step, vk_flagella_step, vk_contact_step, vk_contact_step_channels, vk_population_plan
  *       are introduced by the comment blocks above their declarations.
  *
  * Conventions
@@ -621,6 +621,53 @@ int vk_motility_step(const vk_motility_params *p, int64_t n_agents, int64_t ld, 
                      int32_t substeps, double *motil, double *loc, const int64_t *key,
                      const double *ligand, int32_t nx, int32_t ny, double bound_x, double bound_y,
                      uint64_t *counter, int32_t *bin_lin, int32_t *ix_out, vk_stream_t stream);
+
+/* The multi-flagellar motor: FlagellaActivity.next_update (vivarium/processes/
+ * flagella_activity.py:135-261; Mears et al. 2014, Sneddon et al. 2012) in the
+ * place of MotorActivity -- up to 32 flagella per agent that switch between CCW
+ * and CW on their own, CheY-P as an Ornstein-Uhlenbeck process, a tumble when
+ * any flagellum turns CW, thrust proportional to the flagella count and the
+ * proton motive force.  Sense, receptor and move are vk_motility_step's, with
+ * speed = run_speed * thrust / 250.                                          */
+
+/* Rows of the per-agent FP64 flagella array flag[VK_FLAG_ROWS][ld]. */
+enum vk_flag_row {
+    VK_FLAG_CHEY = 0,             /* CheY (uM)                                     */
+    VK_FLAG_CHEY_P = 1,           /* CheY_P (uM)                                   */
+    VK_FLAG_CW_BIAS = 2,          /* cw_bias: emitted, read by nothing             */
+    VK_FLAG_MOTILE_STATE = 3,     /* motile_state: -1 run, 0 none, 1 tumble        */
+    VK_FLAG_PMF = 4,              /* proton motive force (mV): set by the user     */
+    VK_FLAG_ROWS = 5
+};
+
+/* Rows of the per-agent int32 flagella array flag_int[VK_FLAGI_ROWS][ld]. */
+enum vk_flagi_row {
+    VK_FLAGI_TARGET = 0,          /* n_flagella wanted (used clamped into [0, 32]) */
+    VK_FLAGI_HAVE = 1,            /* flagella the agent has                        */
+    VK_FLAGI_MASK = 2,            /* bit i set: flagellum i turns CW; bits >= have are 0 */
+    VK_FLAGI_ROWS = 3
+};
+
+/* FlagellaActivity.defaults, the parameters next_update reads. */
+typedef struct vk_flagella_params {
+    double YP_ss, sigma2_Y, tau;         /* CheY-P fluctuations: uM, uM^2, s          */
+    double K_d, H;                       /* CW bias Hill curve                        */
+    double omega, g_0, g_1, K_D;         /* a flagellum's switch                      */
+    double flagellum_thrust;             /* pN per flagellum                          */
+    double tumble_scaling, run_scaling;  /* 1 / mV                                    */
+} vk_flagella_params;
+
+/* As vk_motility_step (same counter, keys, bins; p supplies the receptor, the
+ * kinematic constants and the seed), with the flagella motor: motil's n_methyl,
+ * activity, motor_state (1 tumbling, else 0), angle, thrust and torque rows are
+ * written, its coarse-motor rows (CheY_P, ccw_motor_bias, ccw_to_cw) are not
+ * touched; flag and flag_int ([rows][ld]) are updated in place except PMF and
+ * target, which are read.  The Philox paths are listed in vk_flagella.hip.   */
+int vk_flagella_step(const vk_motility_params *p, const vk_flagella_params *f, int64_t n_agents,
+                     int64_t ld, double dt, int32_t substeps, double *motil, double *flag,
+                     int32_t *flag_int, double *loc, const int64_t *key, const double *ligand,
+                     int32_t nx, int32_t ny, double bound_x, double bound_y, uint64_t *counter,
+                     int32_t *bin_lin, int32_t *ix_out, vk_stream_t stream);
 
 /* Occupancy on the device: order[k] = the agent column with the k-th smallest
  * (bin_lin[a], key[a]) (key NULL: the column index; keys distinct, < 2^32),

@@ -24,6 +24,9 @@ motor update (the reference's chemoreceptor_cluster.py / coarse_motor.py), it
 runs or tumbles (this engine's kinematics, not the reference's multibody), and
 the bins and their agent-ordered occupancy are rebuilt on the device -- then
 the step above, with the exchange going into the bin the agent has reached.
+A model with ``flagella=FlagellaModel(...)`` runs the reference's multi-flagellar
+motor (flagella_activity.py) in the coarse motor's place, on two more per-agent
+arrays (``flag``, ``flag_int``); :meth:`Colony.set_flagella` changes the counts.
 
 With a :class:`~lens_amd.mechanics.ContactModel` (``mechanics=``) the step starts
 with the contact launch instead: overlapping capsules push each other apart
@@ -69,7 +72,8 @@ from lens_amd.configs import initial_conc
 from lens_amd.kinetics import KineticsEngine
 from lens_amd.lattice import Lattice, occupancy, segment_index, N_A_LEGACY
 from lens_amd.mechanics import ContactBuffers, ContactModel, contact_step
-from lens_amd.motility import DeviceOccupancy, MotilityModel, ROW_NAMES as MOTIL_ROW_NAMES, motility_step
+from lens_amd.motility import (DeviceOccupancy, MotilityModel, ROW_NAMES as MOTIL_ROW_NAMES, FLAG_ROW_NAMES,
+                               FLAGI_ROW_NAMES, check_flagella_counts, flagella_step, motility_step)
 from lens_amd.rate_law_compiler import compile_rate_laws, RateLawTable
 from lens_amd.response import CellResponse, ResponseBuffers, ResponseEngine
 
@@ -234,6 +238,11 @@ class Colony:
                 # word): on the device, advanced by each launch, so graphs replay it
                 self._motil_counter = z(1, dtype=torch.int64)
                 self._occ_dev = DeviceOccupancy(ld, dev)
+                if motility.flagella is not None:
+                    # the multi-flagellar motor's state: FP64 rows, and count / count / mask
+                    flag, flag_int = motility.flagella.initial_rows(self.n, ld, motility.seed)
+                    self.flag = torch.from_numpy(flag).to(dev).contiguous()
+                    self.flag_int = torch.from_numpy(flag_int).to(dev).contiguous()
             if mechanics is not None:
                 if cells is None:
                     self.mech_angle = torch.from_numpy(mechanics.initial_angles(self.n, ld)).to(dev).contiguous()
@@ -318,6 +327,29 @@ class Colony:
             put(self.location, location)
             self.refresh_bins()
 
+    def set_flagella(self, counts):
+        """The flagella count each agent is to have (the reference's ``internal_counts``
+        ``flagella``): an int for every agent, or one value per agent column [0, n) as a
+        host array or a device int32 tensor.  The next inner update grows or removes
+        flagella to match.  The values are copied into the existing ``flag_int`` row, so a
+        captured graph sees them at its next replay.  Host values outside 0..32 raise; a
+        device tensor is not read back, and the kernel clamps what it finds."""
+        if self.motility is None or self.motility.flagella is None:
+            raise ValueError('set_flagella: a colony with motility=MotilityModel(flagella=FlagellaModel(...))')
+        row = self.flag_int[native.VK_FLAGI_TARGET, :self.n]
+        if torch.is_tensor(counts) and counts.device.type == self.device.type and self.device.type != 'cpu':
+            if counts.dtype != torch.int32 or counts.dim() != 1 or counts.shape[0] < self.n:
+                raise ValueError('set_flagella: a device tensor must be int32 over agents [0, n)')
+            row.copy_(counts[:self.n])
+            return
+        c = check_flagella_counts(counts.cpu().numpy() if torch.is_tensor(counts) else counts)
+        if c.ndim == 0:
+            row.fill_(int(c))
+        else:
+            if c.shape[0] < self.n:
+                raise ValueError('set_flagella: one count per agent (%d < %d)' % (c.shape[0], self.n))
+            row.copy_(torch.from_numpy(c[:self.n].astype(np.int32)))
+
     def agent_array_names(self):
         """Every per-agent array (agent = column), as attribute names: what
         division gathers and the router migrates."""
@@ -330,6 +362,8 @@ class Colony:
             names += ['dead', 'frozen']
         if getattr(self, 'motility', None) is not None:
             names.append('motil')
+            if self.motility.flagella is not None:
+                names += ['flag', 'flag_int']
         if getattr(self, 'mechanics', None) is not None and self.cells is None:
             names.append('mech_angle')
         if self.ordinal is not None:
@@ -713,8 +747,13 @@ class Colony:
         re-layout: ``_layout`` stays, captured graphs stay valid."""
         if self.router is not None:
             raise ValueError('a motile colony takes no router')
-        motility_step(self.motility, self.lattice, self.location, self.motil, self.n, dt, self._motil_counter,
-                      key=getattr(self, 'agent_order', None), bin_lin=self.bin_lin, bin_ix=self.bin_ix)
+        key = getattr(self, 'agent_order', None)
+        if self.motility.flagella is not None:
+            flagella_step(self.motility, self.lattice, self.location, self.motil, self.flag, self.flag_int, self.n,
+                          dt, self._motil_counter, key=key, bin_lin=self.bin_lin, bin_ix=self.bin_ix)
+        else:
+            motility_step(self.motility, self.lattice, self.location, self.motil, self.n, dt, self._motil_counter,
+                          key=key, bin_lin=self.bin_lin, bin_ix=self.bin_ix)
         if self.exchange_mode == 'sorted' and self.map_exch_count.numel():
             lat = self.lattice
             self._occ_dev.sort(self.bin_lin, self.n, lat.rows_local * lat.ny, getattr(self, 'agent_order', None))
@@ -1287,6 +1326,12 @@ class Colony:
         if self.motility is not None:
             m = self.motil[:, :self.n].cpu().numpy()
             out['motility'] = {name: m[row].copy() for row, name in enumerate(MOTIL_ROW_NAMES)}
+            if self.motility.flagella is not None:
+                f = self.flag[:, :self.n].cpu().numpy()
+                fi = self.flag_int[:, :self.n].cpu().numpy()
+                out['flagella'] = {name: f[row].copy() for row, name in enumerate(FLAG_ROW_NAMES)}
+                out['flagella'].update({name: fi[row].copy() for row, name in enumerate(FLAGI_ROW_NAMES)})
+                out['flagella']['mask'] = out['flagella']['mask'].view(np.uint32)     # bit i: flagellum i is CW
         if self.mechanics is not None:
             angle = self.cell[native.VK_CELL_ANGLE] if self.cells is not None else self.mech_angle
             out['mechanics'] = {'angle': angle[:self.n].cpu().numpy().copy(),

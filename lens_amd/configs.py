@@ -270,5 +270,17 @@ def mother_machine(n_agents=3, bounds=(20.0, 20.0), n_bins=(10, 10), channel_spa
     }
 
 
+def chemotaxis_variable_flagella(n_flagella=5, **motility):
+    """The reference's ChemotaxisVariableFlagella compartment (vivarium/compartments/
+    chemotaxis_flagella.py:55-91) as a MotilityModel: the receptor cluster at ligand
+    ``MeAsp``, initial ligand 1e-2 mM, and FlagellaActivity with ``n_flagella`` (one
+    count, or one per agent) in the place of the coarse motor.  Further keyword
+    arguments (``substeps``, ``seed``, ...) go to the MotilityModel."""
+    from lens_amd.motility import FlagellaModel, MotilityModel
+    motility.setdefault('ligand_id', 'MeAsp')
+    motility.setdefault('initial_ligand', 1e-2)
+    return MotilityModel(flagella=FlagellaModel(n_flagella), **motility)
+
+
 def deepcopy_config(cfg):
     return copy.deepcopy(cfg)

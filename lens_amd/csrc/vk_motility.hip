@@ -16,7 +16,8 @@
 // rigid-body simulation (multibody); this engine has no multibody physics, and moves each
 // agent with its own stand-in: a constant run speed along the heading, a slower drift and a
 // Gaussian heading change while tumbling, reflecting walls.  thrust / torque are still
-// emitted (250 / 0 running, 100 / d(angle)/dt tumbling).
+// emitted (250 / 0 running, 100 / d(angle)/dt tumbling); the speed is run_speed * thrust / 250.
+// Receptor, tumble and move are shared with the flagella kernel (vk_motile.h).
 //
 // Random numbers: draw j in {0, 1, 2} of the agent with reference-order key k at global
 // inner update s is philox_uniform(seed, s, k, 0, j) -- independent of storage order and
@@ -26,12 +27,7 @@
 // A streaming kernel: per agent it reads and writes 9 state rows and the location once, and
 // reads one ligand value per inner update; the state of an agent lives in registers between.
 
-#include <math.h>
-#include <stdint.h>
-
-#include "vk_bin.h"
-#include "vk_internal.h"
-#include "vk_philox.h"
+#include "vk_motile.h"
 
 __global__ __launch_bounds__(256) void k_motility_step(vk_motility_params p, int64_t n, int64_t ld, double h,
                                                        int substeps, double *__restrict__ motil,
@@ -62,27 +58,8 @@ __global__ __launch_bounds__(256) void k_motility_step(vk_motility_params p, int
         // (a) sense: the plane is not written here, so this is the pre-step field
         const double L = ligand[bin];
 
-        // (b) receptor.  The reference's quirk is kept: an out-of-range n_methyl is
-        // clamped and not advanced in that update
-        if (n_methyl < 0.0) {
-            n_methyl = 0.0;
-        } else if (n_methyl > 8.0) {
-            n_methyl = 8.0;
-        } else {
-            const double d_methyl = p.adapt_rate * (p.k_meth * CheR * (1.0 - P_on) - p.k_demeth * CheB * P_on) * h;
-            n_methyl += d_methyl;
-        }
-        double offset_energy;
-        if (n_methyl < 0.0) offset_energy = 1.0;
-        else if (n_methyl < 2.0) offset_energy = 1.0 - 0.5 * n_methyl;
-        else if (n_methyl < 4.0) offset_energy = -0.3 * (n_methyl - 2.0);
-        else if (n_methyl < 6.0) offset_energy = -0.6 - 0.25 * (n_methyl - 4.0);
-        else if (n_methyl < 7.0) offset_energy = -1.1 - 0.9 * (n_methyl - 6.0);
-        else if (n_methyl < 8.0) offset_energy = -2.0 - (n_methyl - 7.0);
-        else offset_energy = -3.0;
-        const double Tar = p.n_Tar * (offset_energy + log((1.0 + L / p.K_Tar_off) / (1.0 + L / p.K_Tar_on)));
-        const double Tsr = p.n_Tsr * (offset_energy + log((1.0 + L / p.K_Tsr_off) / (1.0 + L / p.K_Tsr_on)));
-        P_on = 1.0 / (1.0 + exp(Tar + Tsr));
+        // (b) receptor (vk_motile.h; the clamp quirk is kept there)
+        motile_receptor(p, CheR, CheB, L, h, n_methyl, P_on);
 
         // (c) motor, from the activity just computed
         CheY_P = p.adapt_precision * p.k_y * p.k_s * P_on / (p.k_y * p.k_s * P_on + p.k_z + p.gamma_Y);
@@ -101,39 +78,15 @@ __global__ __launch_bounds__(256) void k_motility_step(vk_motility_params p, int
         // (d) kinematics: this engine's stand-in for the reference's pymunk multibody
         double speed;
         if (tumbling) {
-            const double u1 = philox_uniform(p.seed, step, k, 0, 1);
-            const double u2 = philox_uniform(p.seed, step, k, 0, 2);
-            const double z = sqrt(-2.0 * log(1.0 - u1)) * cos(6.283185307179586 * u2);   // Box-Muller
-            const double d_angle = p.tumble_sigma * h * z;
-            angle += d_angle;
+            torque = motile_tumble(p, step, k, h, angle);
             speed = p.run_speed * 100.0 / 250.0;
             thrust = 100.0;
-            torque = d_angle / h;
         } else {
             speed = p.run_speed;
             thrust = 250.0;
             torque = 0.0;
         }
-        x += speed * h * cos(angle);
-        y += speed * h * sin(angle);
-        // reflecting walls: mirror the coordinate and the heading, then clamp into [0, bound)
-        if (x < 0.0) {
-            x = -x;
-            angle = M_PI - angle;
-        } else if (x >= bx) {
-            x = 2.0 * bx - x;
-            angle = M_PI - angle;
-        }
-        if (y < 0.0) {
-            y = -y;
-            angle = -angle;
-        } else if (y >= by) {
-            y = 2.0 * by - y;
-            angle = -angle;
-        }
-        x = fmin(fmax(x, 0.0), bx_below);
-        y = fmin(fmax(y, 0.0), by_below);
-        bin = bin_site_lin(x, y, nx, ny, bx, by, 0, &ix);
+        bin = motile_move(speed, h, angle, x, y, nx, ny, bx, by, bx_below, by_below, &ix);
     }
     motil[(int64_t)VK_MOTIL_N_METHYL * ld + a] = n_methyl;
     motil[(int64_t)VK_MOTIL_ACTIVITY * ld + a] = P_on;
@@ -148,11 +101,6 @@ __global__ __launch_bounds__(256) void k_motility_step(vk_motility_params p, int
     loc[ld + a] = y;
     bin_lin[a] = bin;
     if (ix_out) ix_out[a] = ix;
-}
-
-// after the agents' kernel, in stream order: the next call's first inner update
-__global__ void k_motility_advance(uint64_t *counter, uint64_t by) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) counter[0] += by;
 }
 
 extern "C" int vk_motility_step(const vk_motility_params *p, int64_t n, int64_t ld, double dt, int32_t substeps,
@@ -174,6 +122,6 @@ extern "C" int vk_motility_step(const vk_motility_params *p, int64_t n, int64_t 
         if (rc) return rc;
     }
     // the counter advances for an empty colony too: s counts inner updates, not agents
-    hipLaunchKernelGGL(k_motility_advance, dim3(1), dim3(64), 0, s, counter, (uint64_t)substeps);
-    return vk::launch_check("k_motility_advance");
+    hipLaunchKernelGGL(k_motile_advance, dim3(1), dim3(64), 0, s, counter, (uint64_t)substeps);
+    return vk::launch_check("k_motile_advance");
 }

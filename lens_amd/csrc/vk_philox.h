@@ -1,6 +1,6 @@
 // Philox4x32-10 (Salmon et al., SC'11), counter-based: u depends only on
 // (seed, step, lineage), never on agent order or launch geometry.  Shared by the
-// growth process (vk_cells.hip) and the motility kernel (vk_motility.hip);
+// growth process (vk_cells.hip) and the motile-agent kernels (vk_motility.hip, vk_flagella.hip);
 // restated on the host by oracle.colony.philox_uniform.
 #pragma once
 

@@ -14,6 +14,13 @@ NOT: the reference hands thrust and torque to pymunk (multibody), which this
 engine does not have.  Agents run at ``run_speed`` along their heading, drift
 at 100/250 of it while tumbling with a Gaussian heading change of
 ``tumble_sigma`` rad/s, and reflect off the lattice bounds.
+
+``MotilityModel(..., flagella=FlagellaModel(n_flagella))`` swaps the coarse
+motor for the reference's ``FlagellaActivity``
+(vivarium/processes/flagella_activity.py): up to 32 flagella per agent that
+switch on their own, CheY-P as an Ornstein-Uhlenbeck process, a tumble when
+any flagellum turns CW, thrust from the flagella count and the proton motive
+force (vk_flagella_step).  The speed then is ``run_speed * thrust / 250``.
 """
 
 from __future__ import annotations
@@ -45,6 +52,89 @@ MOTOR_DEFAULTS = {
 
 ROW_NAMES = ('n_methyl', 'chemoreceptor_activity', 'CheY_P', 'ccw_motor_bias', 'ccw_to_cw', 'motor_state',
              'angle', 'thrust', 'torque')          # vk_motil_row order
+
+
+# FlagellaActivity.defaults (flagella_activity.py:48-86), verbatim; next_update reads YP_ss,
+# sigma2_Y, tau, K_d, H, omega, g_0, g_1, K_D, flagellum_thrust and the two scalings
+FLAGELLA_INITIAL_PMF = 170
+FLAGELLA_DEFAULTS = {
+    'n_flagella': 5,
+    'initial_state': {'CheY': 2.59, 'CheY_P': 2.59, 'cw_bias': 0.5, 'motile_state': 0, 'PMF': FLAGELLA_INITIAL_PMF},
+    'ccw_to_cw': 0.26, 'cw_to_ccw': 1.7, 'CB': 0.13, 'lambda': 0.68,
+    'YP_ss': 2.59, 'sigma2_Y': 1.0, 'tau': 0.2,
+    'K_d': 3.1, 'H': 10.3,
+    'omega': 1.3, 'g_0': 40, 'g_1': 40, 'K_D': 3.06,
+    'flagellum_thrust': 25, 'tumble_jitter': 120.0,
+    'tumble_scaling': 1 / FLAGELLA_INITIAL_PMF, 'run_scaling': 1 / FLAGELLA_INITIAL_PMF,
+    'time_step': 0.01,
+}
+FLAG_ROW_NAMES = ('CheY', 'CheY_P', 'cw_bias', 'motile_state', 'PMF')      # vk_flag_row order
+FLAGI_ROW_NAMES = ('target', 'have', 'mask')                                # vk_flagi_row order
+MAX_FLAGELLA = 32
+
+
+def check_flagella_counts(counts):
+    """``counts`` (an int or an array of ints) as an int64 array, every value in 0..32."""
+    c = np.asarray(counts)
+    if c.dtype.kind not in 'iu' and not (c.dtype.kind == 'f' and np.all(c == np.floor(c))):
+        raise ValueError('flagella counts must be whole numbers')
+    c = c.astype(np.int64)
+    if c.ndim > 1 or (c.size and (c.min() < 0 or c.max() > MAX_FLAGELLA)):
+        raise ValueError('flagella counts must lie in 0..%d (one value, or one per agent)' % MAX_FLAGELLA)
+    return c
+
+
+class FlagellaModel:
+    """The reference's ``FlagellaActivity`` (vivarium/processes/flagella_activity.py):
+    its default parameters and initial state.  ``n_flagella`` is one count for
+    every agent or one per agent, 0..32.  ``MotilityModel(flagella=FlagellaModel())``
+    runs it in the place of the coarse motor (vk_flagella_step)."""
+
+    def __init__(self, n_flagella=5, **parameters):
+        unknown = set(parameters) - set(FLAGELLA_DEFAULTS)
+        if unknown:
+            raise ValueError('unknown flagella parameters: %s' % sorted(unknown))
+        initial = parameters.pop('initial_state', None) or {}
+        unknown = set(initial) - set(FLAGELLA_DEFAULTS['initial_state'])
+        if unknown:
+            raise ValueError('unknown flagella initial states: %s' % sorted(unknown))
+        self.n_flagella = check_flagella_counts(n_flagella)
+        self.parameters = dict(FLAGELLA_DEFAULTS, **parameters)
+        self.parameters['n_flagella'] = n_flagella
+        self.parameters['initial_state'] = dict(FLAGELLA_DEFAULTS['initial_state'], **initial)
+        if not self.parameters['tau'] > 0 or self.parameters['sigma2_Y'] < 0:
+            raise ValueError('flagella: tau > 0 and sigma2_Y >= 0')
+
+    def counts(self, n: int) -> np.ndarray:
+        c = self.n_flagella
+        if c.ndim == 0:
+            return np.full(n, int(c), dtype=np.int64)
+        if c.shape[0] < n:
+            raise ValueError('n_flagella must give every agent a count (%d < %d)' % (c.shape[0], n))
+        return c[:n]
+
+    def initial_rows(self, n: int, ld: int, seed: int = 0):
+        """(flag [VK_FLAG_ROWS, ld] float64, flag_int [VK_FLAGI_ROWS, ld] int32): the
+        reference's initial_state; have = target = n_flagella, and each flagellum CW
+        with probability 1/2 from a numpy generator seeded with ``seed``."""
+        flag = np.zeros((native.VK_FLAG_ROWS, ld))
+        for row, name in enumerate(FLAG_ROW_NAMES):
+            flag[row, :n] = self.parameters['initial_state'][name]
+        flag_int = np.zeros((native.VK_FLAGI_ROWS, ld), dtype=np.int32)
+        have = self.counts(n)
+        cw = np.random.default_rng(seed).random((n, MAX_FLAGELLA)) < 0.5
+        cw &= np.arange(MAX_FLAGELLA)[None, :] < have[:, None]
+        mask = (cw.astype(np.uint64) << np.arange(MAX_FLAGELLA, dtype=np.uint64)[None, :]).sum(axis=1)
+        flag_int[native.VK_FLAGI_TARGET, :n] = have
+        flag_int[native.VK_FLAGI_HAVE, :n] = have
+        flag_int[native.VK_FLAGI_MASK, :n] = mask.astype(np.uint32).view(np.int32)
+        return flag, flag_int
+
+    def vk_params(self) -> native.VkFlagellaParams:
+        f = native.VkFlagellaParams()
+        for name, _ in native.VkFlagellaParams._fields_:
+            setattr(f, name, float(self.parameters[name]))
+        return f
 
 
 def receptor_update(p, n_methyl, P_on, ligand, timestep):
@@ -80,7 +170,9 @@ def receptor_update(p, n_methyl, P_on, ligand, timestep):
 class MotilityModel:
     def __init__(self, ligand_id: str = 'MeAsp', initial_ligand: float = 5.0, receptor: Optional[dict] = None,
                  motor: Optional[dict] = None, run_speed: float = 14.0, tumble_sigma: float = math.radians(120.0),
-                 substeps: int = 1, seed: int = 0, angles=None):
+                 substeps: int = 1, seed: int = 0, angles=None, flagella: Optional[FlagellaModel] = None):
+        if flagella is not None and not isinstance(flagella, FlagellaModel):
+            raise ValueError('flagella must be a FlagellaModel')
         for given, known, what in ((receptor, RECEPTOR_DEFAULTS, 'receptor'), (motor, MOTOR_DEFAULTS, 'motor')):
             unknown = set(given or {}) - set(known)
             if unknown:
@@ -96,6 +188,7 @@ class MotilityModel:
         self.substeps = int(substeps)
         self.seed = int(seed)
         self.angles = angles                     # initial headings (rad) per agent; None: seeded uniform
+        self.flagella = flagella                 # None: the coarse motor (vk_motility_step)
         # run_to_steady_state(self, initial_state, 1.0) (chemoreceptor_cluster.py:36-46, :126)
         n_methyl, P_on = self.receptor['n_methyl'], self.receptor['chemoreceptor_activity']
         delta, self.steady_iterations = 1, 0
@@ -160,6 +253,36 @@ def motility_step(model: MotilityModel, lattice, location, motil, n: int, dt: fl
         native.ptr(location), native.ptr(key), native.ptr(plane), lattice.n_bins[0], lattice.n_bins[1],
         lattice.bounds[0], lattice.bounds[1], native.ptr(counter), native.ptr(bin_lin), native.ptr(bin_ix),
         native.stream_handle()), 'vk_motility_step')
+    return bin_lin
+
+
+def flagella_step(model: MotilityModel, lattice, location, motil, flag, flag_int, n: int, dt: float, counter,
+                  key=None, bin_lin=None, bin_ix=None, substeps: Optional[int] = None):
+    """One vk_flagella_step launch on the current stream: :func:`motility_step` with
+    ``model.flagella``'s motor in the place of the coarse one, on ``flag``
+    [VK_FLAG_ROWS, ld] (float64) and ``flag_int`` [VK_FLAGI_ROWS, ld] (int32)."""
+    import torch
+    if model.flagella is None:
+        raise ValueError('flagella_step: the model has no FlagellaModel')
+    if lattice.pad_top or lattice.pad_bot or not (lattice.edge_top and lattice.edge_bot):
+        raise ValueError('flagella_step: a whole, unbanded plane')
+    ld = location.shape[1]
+    if motil.shape != (native.VK_MOTIL_ROWS, ld) or not (motil.is_contiguous() and location.is_contiguous()):
+        raise ValueError('flagella_step: motil must be [VK_MOTIL_ROWS, ld] beside location [2, ld], contiguous')
+    if (flag.shape != (native.VK_FLAG_ROWS, ld) or flag.dtype != torch.float64 or not flag.is_contiguous() or
+            flag_int.shape != (native.VK_FLAGI_ROWS, ld) or flag_int.dtype != torch.int32 or
+            not flag_int.is_contiguous()):
+        raise ValueError('flagella_step: flag must be float64 [VK_FLAG_ROWS, ld] and flag_int int32 '
+                         '[VK_FLAGI_ROWS, ld], contiguous')
+    if bin_lin is None:
+        bin_lin = torch.zeros(ld, dtype=torch.int32, device=location.device)
+    plane = lattice.fields[lattice.molecules.index(model.ligand_id)]
+    p, f = model.vk_params(), model.flagella.vk_params()
+    native.check(native._lib.vk_flagella_step(
+        ctypes.byref(p), ctypes.byref(f), n, ld, float(dt), int(model.substeps if substeps is None else substeps),
+        native.ptr(motil), native.ptr(flag), native.ptr(flag_int), native.ptr(location), native.ptr(key),
+        native.ptr(plane), lattice.n_bins[0], lattice.n_bins[1], lattice.bounds[0], lattice.bounds[1],
+        native.ptr(counter), native.ptr(bin_lin), native.ptr(bin_ix), native.stream_handle()), 'vk_flagella_step')
     return bin_lin
 
 

@@ -35,6 +35,7 @@ EXPORTS = (
     'vk_exchange_ordered', 'vk_contact_scratch_bytes', 'vk_contact_step',
     'vk_response_begin', 'vk_response_end', 'vk_response_cells', 'vk_exchange_ordered_mixed',
     'vk_exchange_atomic_f64', 'vk_population_scratch_bytes', 'vk_population_plan', 'vk_contact_step_channels',
+    'vk_flagella_step',
 )
 
 VK_CELL_MASS, VK_CELL_VOLUME, VK_CELL_LENGTH, VK_CELL_SURFACE_AREA, VK_CELL_PROTEIN, VK_CELL_ANGLE = range(6)
@@ -42,6 +43,10 @@ VK_CELL_ROWS = 6
 (VK_MOTIL_N_METHYL, VK_MOTIL_ACTIVITY, VK_MOTIL_CHEY_P, VK_MOTIL_CCW_MOTOR_BIAS, VK_MOTIL_CCW_TO_CW,
  VK_MOTIL_MOTOR_STATE, VK_MOTIL_ANGLE, VK_MOTIL_THRUST, VK_MOTIL_TORQUE) = range(9)
 VK_MOTIL_ROWS = 9
+VK_FLAG_CHEY, VK_FLAG_CHEY_P, VK_FLAG_CW_BIAS, VK_FLAG_MOTILE_STATE, VK_FLAG_PMF = range(5)
+VK_FLAG_ROWS = 5
+VK_FLAGI_TARGET, VK_FLAGI_HAVE, VK_FLAGI_MASK = range(3)
+VK_FLAGI_ROWS = 3
 VK_GROWTH_PROTEIN, VK_GROWTH_MASS = 0, 1
 VK_RNG_STREAM, VK_RNG_PHILOX = 0, 1
 VK_DIVIDE_SET, VK_DIVIDE_SPLIT, VK_DIVIDE_ZERO = 0, 1, 2
@@ -97,6 +102,12 @@ class VkMotilityParams(ctypes.Structure):
         'n_Tar', 'n_Tsr', 'K_Tar_off', 'K_Tar_on', 'K_Tsr_off', 'K_Tsr_on', 'k_meth', 'k_demeth', 'adapt_rate',
         'CheR', 'CheB', 'k_y', 'k_s', 'k_z', 'gamma_Y', 'adapt_precision', 'mb_0', 'cw_to_ccw',
         'cw_to_ccw_leak', 'run_speed', 'tumble_sigma')] + [('seed', ctypes.c_uint64)]
+
+
+class VkFlagellaParams(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_double) for n in (
+        'YP_ss', 'sigma2_Y', 'tau', 'K_d', 'H', 'omega', 'g_0', 'g_1', 'K_D', 'flagellum_thrust',
+        'tumble_scaling', 'run_scaling')]
 
 
 class VkContactParams(ctypes.Structure):
@@ -163,6 +174,8 @@ _SIGS = {
                           _vp, _vp, _f64, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     'vk_motility_step': ([ctypes.POINTER(VkMotilityParams), _i64, _i64, _f64, _i32, _vp, _vp, _vp, _vp, _i32, _i32,
                           _f64, _f64, _vp, _vp, _vp, _vp], ctypes.c_int),
+    'vk_flagella_step': ([ctypes.POINTER(VkMotilityParams), ctypes.POINTER(VkFlagellaParams), _i64, _i64, _f64, _i32,
+                          _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f64, _f64, _vp, _vp, _vp, _vp], ctypes.c_int),
     'vk_occupancy_scratch_bytes': ([_i64], ctypes.c_int64),
     'vk_occupancy_sort': ([_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp], ctypes.c_int),
     'vk_exchange_ordered': ([_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _f64, _vp], ctypes.c_int),
