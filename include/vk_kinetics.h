@@ -35,7 +35,8 @@
  *   vk_bin_sites
  *       replaces get_bin_site (vivarium/library/lattice_utils.py:18-40).
  *   vk_cell_step / vk_divide_*, vk_kremling_step, vk_expression_step,
- *   vk_motility_step, vk_flagella_step, vk_contact_step, vk_contact_step_channels, vk_population_plan
+ *   vk_motility_step, vk_flagella_step, vk_contact_step, vk_contact_step_channels, vk_population_plan,
+ *   vk_flagella_counts, vk_divide_flagella
  *       are introduced by the comment blocks above their declarations.
  *
  * Conventions
@@ -668,6 +669,72 @@ int vk_flagella_step(const vk_motility_params *p, const vk_flagella_params *f, i
                      int32_t *flag_int, double *loc, const int64_t *key, const double *ligand,
                      int32_t nx, int32_t ny, double bound_x, double bound_y, uint64_t *counter,
                      int32_t *bin_lin, int32_t *ix_out, vk_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Motile agents that grow and divide (the reference's ChemotaxisODEExpressionFlagella,
+ * vivarium/compartments/chemotaxis_flagella.py:94-173)
+ *
+ *   vk_flagella_counts
+ *       replaces the counts deriver of ODE_expression for the flagella protein
+ *       (vivarium/processes/derive_counts.py:42-51: counts = int(concentration *
+ *       mmol_to_counts)), whose result FlagellaActivity reads as n_flagella
+ *       (flagella_activity.py:138,155).  It runs after the expression update and
+ *       before DeriveGlobals (Generator.generate, core/process.py:75-103,179-182:
+ *       generated derivers first, in process order), so mmol_to_counts is the
+ *       value the previous step's DeriveGlobals left.
+ *   vk_divide_flagella
+ *       replaces, for flag_int and the agents' motility keys, the `_divide` branch
+ *       of Store.apply_update (core/experiment.py:664-697) with divide_split on the
+ *       int count (core/registry.py:205-227) and the flagella's split_dict
+ *       (flagella_activity.py:126-131, core/registry.py:246-262) -- either as
+ *       declared, or as deep_merge (library/dict_utils.py:51-66) leaves it: the
+ *       daughters start as deep copies of the mother and merging a divided dict into
+ *       a copy only adds or overwrites keys, so both keep every flagellum.
+ * ------------------------------------------------------------------------- */
+
+/* target[a] = clamp(trunc(conc[a] * m2c[a]), 0, 32) for a < n: one FP64 multiply,
+ * truncated toward zero like Python's int(); NaN and negative products give 0.
+ * flags: one device int32, set to 1 (never cleared) when any product lay outside
+ * [0, 33) -- the reference would fail there, or grow past the 32 flagella of the
+ * mask.  No host synchronisation; the launch is the same inside a captured graph. */
+int vk_flagella_counts(int64_t n_agents, const double *conc, const double *mmol_to_counts,
+                       int32_t *target, int32_t *flags, vk_stream_t stream);
+
+enum vk_flagella_divider {
+    VK_FLAGELLA_MERGED = 0,      /* what the reference's Store does: both daughters keep every
+                                    flagellum of the mother (have and mask copied); the split
+                                    target makes each shed the surplus in her first update   */
+    VK_FLAGELLA_SPLIT_DICT = 1   /* the declared divider: with h = have / 2, daughter 0 gets the
+                                    flagella [h, have) (have - h, mask >> h), daughter 1 the
+                                    flagella [0, h) (h, mask & ((1 << h) - 1))               */
+};
+
+/* Mixed into the seed of vk_divide_flagella's draw (seed ^ this). */
+#define VK_DIVIDE_FLAGELLA_DOMAIN 0x666c6167656c6c61ULL
+
+/* The motile state's dividers over a plan of vk_divide_plan (slots [0, n_keep) are the
+ * survivors, the daughters follow; n_src agents in the source arrays).  flag_int_dst
+ * [VK_FLAGI_ROWS][ld_dst] and key_dst [ld_dst] receive, per slot j with a = src_index[j]:
+ *   survivor    the three rows and key_src[a], copied;
+ *   daughter k  key_base + (j - n_keep), a key no agent has had (the caller advances
+ *               key_base by n_out - n_keep; the last key must not pass 2^31 - 1, the motility
+ *               kernels put it into a 32-bit counter word);
+ *               target: half = t / 2, and the odd one (t - 2 half) to daughter 0 when u < 0.5,
+ *               else to daughter 1; u is one draw per mother, the same for both daughters:
+ *               Philox(key (seed ^ VK_DIVIDE_FLAGELLA_DOMAIN) lo + depth, hi; counter (step,
+ *               root, path lo, path hi)) of the MOTHER's lineage root_src / depth_src /
+ *               path_src -- vk_cell_step's layout under another key, so it coincides neither
+ *               with the growth draw nor with a draw of the motility kernels (counter (s, k,
+ *               j, 0), key seed);
+ *               have, mask: by `mode` (vk_flagella_divider).
+ * flag_int_src and flag_int_dst may both be NULL (the coarse motor has no flagella): keys
+ * only.  No atomics, no host synchronisation.                                       */
+int vk_divide_flagella(int64_t n_out, int64_t n_keep, int64_t n_src, const int32_t *src_index,
+                       const int32_t *kind, const int32_t *flag_int_src, int64_t ld_src,
+                       const int64_t *key_src, const int32_t *root_src, const int32_t *depth_src,
+                       const uint64_t *path_src, int32_t *flag_int_dst, int64_t ld_dst,
+                       int64_t *key_dst, int32_t mode, uint64_t seed, uint64_t step, int64_t key_base,
+                       vk_stream_t stream);
 
 /* Occupancy on the device: order[k] = the agent column with the k-th smallest
  * (bin_lin[a], key[a]) (key NULL: the column index; keys distinct, < 2^32),

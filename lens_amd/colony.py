@@ -27,6 +27,12 @@ the step above, with the exchange going into the bin the agent has reached.
 A model with ``flagella=FlagellaModel(...)`` runs the reference's multi-flagellar
 motor (flagella_activity.py) in the coarse motor's place, on two more per-agent
 arrays (``flag``, ``flag_int``); :meth:`Colony.set_flagella` changes the counts.
+With ``FlagellaModel(expression=...)`` the counts follow an expressed protein instead
+(``flag_expr``: vk_expression_step, then the counts deriver vk_flagella_counts, before
+the growth launch touches ``mmol_to_counts``).  A model with ``division=`` combines with
+``cells=``: the cell's angle is the swimming direction, every agent draws by a key of
+her own (``motile_key``), and division hands the motile state to the daughters with the
+reference's dividers (vk_divide_flagella; the reference's ChemotaxisODEExpressionFlagella).
 
 With a :class:`~lens_amd.mechanics.ContactModel` (``mechanics=``) the step starts
 with the contact launch instead: overlapping capsules push each other apart
@@ -69,10 +75,11 @@ import torch
 from lens_amd import native
 from lens_amd.cells import CellModel, lineage_ids
 from lens_amd.configs import initial_conc
+from lens_amd.expression import ExpressionEngine
 from lens_amd.kinetics import KineticsEngine
 from lens_amd.lattice import Lattice, occupancy, segment_index, N_A_LEGACY
 from lens_amd.mechanics import ContactBuffers, ContactModel, contact_step
-from lens_amd.motility import (DeviceOccupancy, MotilityModel, ROW_NAMES as MOTIL_ROW_NAMES, FLAG_ROW_NAMES,
+from lens_amd.motility import (DeviceOccupancy, DIVISION_MODES, MotilityModel, ROW_NAMES as MOTIL_ROW_NAMES, FLAG_ROW_NAMES,
                                FLAGI_ROW_NAMES, check_flagella_counts, flagella_step, motility_step)
 from lens_amd.rate_law_compiler import compile_rate_laws, RateLawTable
 from lens_amd.response import CellResponse, ResponseBuffers, ResponseEngine
@@ -97,7 +104,8 @@ class Colony:
             raise ValueError('exchange must be sorted or atomic')
         if motility is not None:
             # checked before anything is built: a motile colony moves and re-bins its
-            # agents on the device, on one whole plane (division and row bands: not yet)
+            # agents on the device, on one whole plane (row bands: not yet; division when the
+            # model says how the motile state divides)
             if not isinstance(environment, Lattice):
                 raise ValueError('motility needs a Lattice environment (agents move through its ligand plane)')
             if motility.ligand_id not in environment.molecules:
@@ -105,7 +113,8 @@ class Colony:
                     motility.ligand_id, environment.molecules))
             if environment.pad_top or environment.pad_bot or not (environment.edge_top and environment.edge_bot):
                 raise ValueError('motility needs a whole, unbanded plane (row bands are not supported)')
-            if cells is not None:
+            if cells is not None and motility.division is None:
+                # the model must say how the motile state divides (MotilityModel(division=...))
                 raise ValueError('motility with cells (growth and division) is not supported')
         if mechanics is not None:
             # checked before anything is built, like motility: the contact launch moves and
@@ -243,6 +252,23 @@ class Colony:
                     flag, flag_int = motility.flagella.initial_rows(self.n, ld, motility.seed)
                     self.flag = torch.from_numpy(flag).to(dev).contiguous()
                     self.flag_int = torch.from_numpy(flag_int).to(dev).contiguous()
+                if cells is not None:
+                    # one heading: the cell's angle is the swimming direction, so daughters
+                    # are placed along it (vk_divide_locations); and a key per agent for the
+                    # motility draws that she keeps for life, whoever divides around her
+                    self.cell[native.VK_CELL_ANGLE, :self.n] = self.motil[native.VK_MOTIL_ANGLE, :self.n]
+                    self.motile_key = torch.arange(ld, dtype=torch.int64, device=dev)
+                    self._key_base = self.n
+                if motility.flagella is not None and motility.flagella.expression is not None:
+                    # the flagella count follows the expressed protein (ODE_expression + its
+                    # counts deriver); the derivers run once at t = 0
+                    fm = motility.flagella
+                    self.flag_expr = torch.from_numpy(np.ascontiguousarray(
+                        np.repeat(fm.expression_initial[:, None], ld, axis=1))).to(dev).contiguous()
+                    self._flag_expression = ExpressionEngine(fm.expression_table, dev)
+                    self._flag_expr_update = z(len(fm.expression_table.outputs), ld)
+                    self._flag_flags = z(1, dtype=torch.int32)
+                    self._flagella_counts()
             if mechanics is not None:
                 if cells is None:
                     self.mech_angle = torch.from_numpy(mechanics.initial_angles(self.n, ld)).to(dev).contiguous()
@@ -336,6 +362,9 @@ class Colony:
         device tensor is not read back, and the kernel clamps what it finds."""
         if self.motility is None or self.motility.flagella is None:
             raise ValueError('set_flagella: a colony with motility=MotilityModel(flagella=FlagellaModel(...))')
+        if self.motility.flagella.expression is not None:
+            raise ValueError('set_flagella: the count is derived from the expressed protein every step '
+                             '(FlagellaModel(expression=...)) and would be overwritten')
         row = self.flag_int[native.VK_FLAGI_TARGET, :self.n]
         if torch.is_tensor(counts) and counts.device.type == self.device.type and self.device.type != 'cpu':
             if counts.dtype != torch.int32 or counts.dim() != 1 or counts.shape[0] < self.n:
@@ -364,6 +393,10 @@ class Colony:
             names.append('motil')
             if self.motility.flagella is not None:
                 names += ['flag', 'flag_int']
+                if self.motility.flagella.expression is not None:
+                    names.append('flag_expr')
+            if self.cells is not None:
+                names.append('motile_key')
         if getattr(self, 'mechanics', None) is not None and self.cells is None:
             names.append('mech_angle')
         if self.ordinal is not None:
@@ -747,13 +780,18 @@ class Colony:
         re-layout: ``_layout`` stays, captured graphs stay valid."""
         if self.router is not None:
             raise ValueError('a motile colony takes no router')
-        key = getattr(self, 'agent_order', None)
+        # a dividing colony draws by the agent's own key; its column order is the reference's
+        # agent order, which the occupancy below keeps (key None)
+        key = self.motile_key if self.cells is not None else getattr(self, 'agent_order', None)
         if self.motility.flagella is not None:
             flagella_step(self.motility, self.lattice, self.location, self.motil, self.flag, self.flag_int, self.n,
                           dt, self._motil_counter, key=key, bin_lin=self.bin_lin, bin_ix=self.bin_ix)
         else:
             motility_step(self.motility, self.lattice, self.location, self.motil, self.n, dt, self._motil_counter,
                           key=key, bin_lin=self.bin_lin, bin_ix=self.bin_ix)
+        if self.cells is not None:
+            # one heading: a device row copy in stream order
+            self.cell[native.VK_CELL_ANGLE, :self.n].copy_(self.motil[native.VK_MOTIL_ANGLE, :self.n])
         if self.exchange_mode == 'sorted' and self.map_exch_count.numel():
             lat = self.lattice
             self._occ_dev.sort(self.bin_lin, self.n, lat.rows_local * lat.ny, getattr(self, 'agent_order', None))
@@ -1075,7 +1113,29 @@ class Colony:
         step.interior_graph = g_interior
         return step
 
+    def _flagella_counts(self):
+        """The counts deriver of the flagella protein (derive_counts.py:42-51): ``target``
+        from the current concentration and the current mmol_to_counts."""
+        fm = self.motility.flagella
+        native.check(native._lib.vk_flagella_counts(
+            self.n, self.flag_expr.data_ptr() + fm.count_row * self.ld * 8, native.ptr(self.m2c),
+            self.flag_int.data_ptr() + native.VK_FLAGI_TARGET * self.ld * 4, native.ptr(self._flag_flags),
+            native.stream_handle()), 'vk_flagella_counts')
+
+    def _flagella_check(self):
+        """Raises if a derived flagella count ever left 0..32 (one host read: called where
+        the host reads from the device anyway)."""
+        if getattr(self, '_flag_flags', None) is not None and int(self._flag_flags.item()):
+            raise FloatingPointError('a derived flagella count left 0..32 (concentration * mmol_to_counts was '
+                                     'negative, not a number or 33 and more): the motor holds 32 flagella')
+
     def _finish_step(self, dt):
+        if self.motility is not None and getattr(self, 'flag_expr', None) is not None:
+            # the expression process from the step-start state (ode_expression.py:265-303), then
+            # its counts deriver -- in front of DeriveGlobals (core/process.py:75-103), so with
+            # the mmol_to_counts the previous step left; both before vk_cell_step touches m2c
+            self._flag_expression.step(dt, self.flag_expr, self.n, update=self._flag_expr_update, accumulate=True)
+            self._flagella_counts()
         if self.cells is not None:
             self.grow_and_divide(dt)
         elif self._channels():
@@ -1142,6 +1202,8 @@ class Colony:
             n_out = int(self._n_out.item())
             if self.mechanics is not None:
                 self._mech.check()       # the too-long flag, where the host reads anyway
+            if self.motility is not None:
+                self._flagella_check()   # the count flag, where the host reads anyway
         if self.router is not None:
             # collective every step: the global order of every rank's survivors
             # and daughters (AgentRouter.division_ordinals); then, if any rank
@@ -1217,6 +1279,9 @@ class Colony:
         return n - n_out
 
     def _apply_division(self, n_out, src, kind, ordinal=None):
+        if self.motility is not None and self._key_base + 2 * (n_out - self.n) - 1 > 2 ** 31 - 1:
+            # before any array is gathered into the new layout
+            raise OverflowError('a motility key would pass 2**31 - 1 (the kernels put it into a 32-bit counter word)')
         ld_src = self.ld
         ld = max(self.ld, n_out)
         if n_out > self.ld:
@@ -1252,6 +1317,8 @@ class Colony:
             # daughters' processes are generated anew, so they are not frozen
             self.dead = gather(self.dead)
             self.frozen = gather(self.frozen, Z)
+        if self.motility is not None:
+            self._divide_motile(n_out, src, kind, ld_src, ld, gather)
         root = torch.empty(ld, dtype=torch.int32, device=dev)
         depth = torch.empty(ld, dtype=torch.int32, device=dev)
         path = torch.empty(ld, dtype=torch.int64, device=dev)
@@ -1274,12 +1341,45 @@ class Colony:
             self._mech_buffers()
         if self.response is not None and ld != ld_src:
             self._response_buffers()
+        if self.motility is not None and ld != ld_src:
+            # the occupancy buffers for the new capacity; the Philox counter is not per agent
+            self._occ_dev = DeviceOccupancy(ld, dev)
+            if getattr(self, 'flag_expr', None) is not None:
+                self._flag_expr_update = torch.zeros((self._flag_expr_update.shape[0], ld), dtype=torch.float64,
+                                                     device=dev)
         if self.lattice is not None:
             self.bin_lin = torch.zeros(ld, dtype=torch.int32, device=dev)
             self.bin_ix = torch.zeros(ld, dtype=torch.int32, device=dev)
             self.refresh_bins()
         if int(self._overflow.item()):
             raise OverflowError('a lineage exceeded 64 generations (phylogeny path bits)')
+
+    def _divide_motile(self, n_out, src, kind, ld_src, ld, gather):
+        """The motile state's dividers (called by _apply_division before the lineage arrays
+        are replaced: the split's draw is keyed by the mother's lineage).  The receptor's and
+        the motor's scalars, PMF and the expression's concentrations have no divider: both
+        daughters start with the mother's value.  The flagella count is split, the flagella
+        go by the model's ``division`` mode, daughters get fresh keys (vk_divide_flagella)."""
+        m, dev = self.motility, self.device
+        n_daughters = 2 * (n_out - self.n)           # vk_divide_plan: nobody is removed
+        self.motil = gather(self.motil)
+        flag_int = None
+        if m.flagella is not None:
+            self.flag = gather(self.flag)
+            if getattr(self, 'flag_expr', None) is not None:
+                self.flag_expr = gather(self.flag_expr)
+            flag_int = torch.empty((native.VK_FLAGI_ROWS, ld), dtype=torch.int32, device=dev)
+        key = torch.empty(ld, dtype=torch.int64, device=dev)
+        native.check(native._lib.vk_divide_flagella(
+            n_out, n_out - n_daughters, self.n, native.ptr(src), native.ptr(kind),
+            native.ptr(self.flag_int) if flag_int is not None else 0, ld_src, native.ptr(self.motile_key),
+            native.ptr(self.lin_root), native.ptr(self.lin_depth), native.ptr(self.lin_path), native.ptr(flag_int), ld,
+            native.ptr(key), DIVISION_MODES[m.division], m.seed & (2 ** 64 - 1), self.step_index & (2 ** 64 - 1),
+            self._key_base, native.stream_handle()), 'vk_divide_flagella')
+        if flag_int is not None:
+            self.flag_int = flag_int
+        self.motile_key = key
+        self._key_base += n_daughters
 
     def agent_ids(self):
         """Phylogeny ids of agents 0..n-1 (meta_division.py:15-18)."""
@@ -1296,6 +1396,8 @@ class Colony:
             raise FloatingPointError('agent %d: kernel status %d' % (a, int(st[a])))
         if self.mechanics is not None:
             self._mech.check()
+        if self.motility is not None:
+            self._flagella_check()
 
     # -- views ----------------------------------------------------------------------
     def species(self, port, name):
@@ -1332,6 +1434,12 @@ class Colony:
                 out['flagella'] = {name: f[row].copy() for row, name in enumerate(FLAG_ROW_NAMES)}
                 out['flagella'].update({name: fi[row].copy() for row, name in enumerate(FLAGI_ROW_NAMES)})
                 out['flagella']['mask'] = out['flagella']['mask'].view(np.uint32)     # bit i: flagellum i is CW
+                if getattr(self, 'flag_expr', None) is not None:
+                    e = self.flag_expr[:, :self.n].cpu().numpy()
+                    out['flagella_expression'] = {name: e[row].copy() for row, name in
+                                                  enumerate(self.motility.flagella.expression_names)}
+            if self.cells is not None:
+                out['motile_key'] = self.motile_key[:self.n].cpu().numpy().copy()
         if self.mechanics is not None:
             angle = self.cell[native.VK_CELL_ANGLE] if self.cells is not None else self.mech_angle
             out['mechanics'] = {'angle': angle[:self.n].cpu().numpy().copy(),

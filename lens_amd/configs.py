@@ -282,5 +282,39 @@ def chemotaxis_variable_flagella(n_flagella=5, **motility):
     return MotilityModel(flagella=FlagellaModel(n_flagella), **motility)
 
 
+def flagella_expression():
+    """The reference's flagella expression configuration (get_flagella_expression,
+    vivarium/processes/ode_expression.py:360-400): its four numbers and the protein
+    map, both states starting at zero.  At these rates the transcript settles at 5e-5 mM
+    and the protein gains 4e-9 mM/s: 2 flagella after 630 s, 7 after a 2520-s cell cycle at
+    the initial volume and 14 at the doubled cell's."""
+    return {
+        'transcription_rates': {'flag_RNA': 1e-6},
+        'translation_rates': {'flagella': 8e-5},
+        'degradation_rates': {'flag_RNA': 2e-2},
+        'protein_map': {'flagella': 'flag_RNA'},
+        'initial_state': {'internal': {'flagella': 0.0, 'flag_RNA': 0.0}},
+    }
+
+
+def chemotaxis_ode_expression_flagella(expression=None, division='merged', **motility):
+    """The reference's ChemotaxisODEExpressionFlagella compartment (vivarium/compartments/
+    chemotaxis_flagella.py:94-173; the ``ode_expression`` agent type of its chemotaxis
+    experiment) as what a Colony takes: ``{'cells': CellModel, 'motility': MotilityModel}``
+    for ``Colony(..., **chemotaxis_ode_expression_flagella())``.  GrowthProtein at growth
+    rate 0.000275 from 1339 fg; the receptor cluster at ligand ``MeAsp``, initial ligand
+    1e-2 mM; FlagellaActivity starting without flagella, their count derived from
+    ``expression`` (default :func:`flagella_expression`); the motile state divided as the
+    reference's Store does (``division='merged'``).  Further keyword arguments
+    (``substeps``, ``seed``, ...) go to the MotilityModel."""
+    from lens_amd.cells import CellModel
+    from lens_amd.motility import FlagellaModel, MotilityModel
+    motility.setdefault('ligand_id', 'MeAsp')
+    motility.setdefault('initial_ligand', 1e-2)
+    flagella = FlagellaModel(0, expression=flagella_expression() if expression is None else expression)
+    return {'cells': CellModel(growth_rate=0.000275, initial_mass=1339.0),
+            'motility': MotilityModel(flagella=flagella, division=division, **motility)}
+
+
 def deepcopy_config(cfg):
     return copy.deepcopy(cfg)

@@ -21,6 +21,12 @@ motor for the reference's ``FlagellaActivity``
 switch on their own, CheY-P as an Ornstein-Uhlenbeck process, a tumble when
 any flagellum turns CW, thrust from the flagella count and the proton motive
 force (vk_flagella_step).  The speed then is ``run_speed * thrust / 250``.
+
+``MotilityModel(..., division='merged' | 'split_dict')`` lets such a colony grow and
+divide (``Colony(..., cells=CellModel(...), motility=model)``), and
+``FlagellaModel(0, expression=...)`` derives the flagella count from an expressed
+protein: together the reference's ChemotaxisODEExpressionFlagella agent
+(vk_flagella_counts, vk_divide_flagella).
 """
 
 from __future__ import annotations
@@ -71,6 +77,7 @@ FLAGELLA_DEFAULTS = {
 FLAG_ROW_NAMES = ('CheY', 'CheY_P', 'cw_bias', 'motile_state', 'PMF')      # vk_flag_row order
 FLAGI_ROW_NAMES = ('target', 'have', 'mask')                                # vk_flagi_row order
 MAX_FLAGELLA = 32
+DIVISION_MODES = {None: None, 'merged': native.VK_FLAGELLA_MERGED, 'split_dict': native.VK_FLAGELLA_SPLIT_DICT}
 
 
 def check_flagella_counts(counts):
@@ -88,9 +95,23 @@ class FlagellaModel:
     """The reference's ``FlagellaActivity`` (vivarium/processes/flagella_activity.py):
     its default parameters and initial state.  ``n_flagella`` is one count for
     every agent or one per agent, 0..32.  ``MotilityModel(flagella=FlagellaModel())``
-    runs it in the place of the coarse motor (vk_flagella_step)."""
+    runs it in the place of the coarse motor (vk_flagella_step).
 
-    def __init__(self, n_flagella=5, **parameters):
+    ``expression`` (an ``ODE_expression`` configuration dict, e.g.
+    ``configs.flagella_expression()``) makes the count a derived quantity, as in the
+    reference's ChemotaxisODEExpressionFlagella (chemotaxis_flagella.py:94-173): the
+    colony keeps the configuration's transcripts and proteins per agent
+    (``flag_expr``), advances them every step (vk_expression_step) and sets the count
+    to ``int(concentration of count_of * mmol_to_counts)`` (vk_flagella_counts).
+    ``n_flagella`` then is only the number of flagella the agents start with (the
+    reference's agent: 0).  The configuration's states all live under ``'internal'``;
+    regulators on other ports and a transcription leak (host draws that cannot be
+    replayed) are refused."""
+
+    def __init__(self, n_flagella=5, expression=None, count_of='flagella', **parameters):
+        self.expression, self.count_of, self.expression_table = None, count_of, None
+        if expression is not None:
+            self._compile_expression(expression, count_of)
         unknown = set(parameters) - set(FLAGELLA_DEFAULTS)
         if unknown:
             raise ValueError('unknown flagella parameters: %s' % sorted(unknown))
@@ -104,6 +125,32 @@ class FlagellaModel:
         self.parameters['initial_state'] = dict(FLAGELLA_DEFAULTS['initial_state'], **initial)
         if not self.parameters['tau'] > 0 or self.parameters['sigma2_Y'] < 0:
             raise ValueError('flagella: tau > 0 and sigma2_Y >= 0')
+
+    def _compile_expression(self, config, count_of):
+        from lens_amd.expression import ExpressionTable, RuleSyntaxError
+        if not isinstance(config, dict):
+            raise ValueError('flagella expression must be an ODE_expression configuration dict')
+        leak = config.get('transcription_leak') or {}
+        if leak.get('rate', 0.0) != 0 or leak.get('magnitude', 0.0) != 0:
+            raise ValueError('flagella expression: a transcription_leak draws on the host and cannot be replayed '
+                             '(rate and magnitude must be 0)')
+        for port, name in config.get('regulators', []):
+            if port != 'internal':
+                raise ValueError('flagella expression: regulator (%r, %r) is not on the internal port' % (port, name))
+        initial = (config.get('initial_state') or {}).get('internal', {})
+        names = list(dict.fromkeys(list(config.get('transcription_rates', {})) +
+                                   list(config.get('translation_rates', {})) + list(initial) +
+                                   [name for _, name in config.get('regulators', [])]))
+        if count_of not in names:
+            raise ValueError('flagella expression: count_of=%r is not one of its states %s' % (count_of, names))
+        try:
+            self.expression_table = ExpressionTable(config, [('internal', s) for s in names])
+        except (KeyError, RuleSyntaxError) as e:
+            raise ValueError('flagella expression: %s' % (e.args[0] if e.args else e))
+        self.expression = config
+        self.expression_names = names
+        self.count_row = names.index(count_of)
+        self.expression_initial = np.array([float(initial.get(s, 0.0)) for s in names], dtype=np.float64)
 
     def counts(self, n: int) -> np.ndarray:
         c = self.n_flagella
@@ -170,9 +217,12 @@ def receptor_update(p, n_methyl, P_on, ligand, timestep):
 class MotilityModel:
     def __init__(self, ligand_id: str = 'MeAsp', initial_ligand: float = 5.0, receptor: Optional[dict] = None,
                  motor: Optional[dict] = None, run_speed: float = 14.0, tumble_sigma: float = math.radians(120.0),
-                 substeps: int = 1, seed: int = 0, angles=None, flagella: Optional[FlagellaModel] = None):
+                 substeps: int = 1, seed: int = 0, angles=None, flagella: Optional[FlagellaModel] = None,
+                 division: Optional[str] = None):
         if flagella is not None and not isinstance(flagella, FlagellaModel):
             raise ValueError('flagella must be a FlagellaModel')
+        if division not in DIVISION_MODES:
+            raise ValueError('division must be None, \'merged\' or \'split_dict\' (got %r)' % (division,))
         for given, known, what in ((receptor, RECEPTOR_DEFAULTS, 'receptor'), (motor, MOTOR_DEFAULTS, 'motor')):
             unknown = set(given or {}) - set(known)
             if unknown:
@@ -189,6 +239,10 @@ class MotilityModel:
         self.seed = int(seed)
         self.angles = angles                     # initial headings (rad) per agent; None: seeded uniform
         self.flagella = flagella                 # None: the coarse motor (vk_motility_step)
+        # how the motile state divides in a colony with cells=: None refuses such a colony;
+        # 'merged' is what the reference's Store does (both daughters keep every flagellum),
+        # 'split_dict' the divider FlagellaActivity declares.  No effect without cells
+        self.division = division
         # run_to_steady_state(self, initial_state, 1.0) (chemoreceptor_cluster.py:36-46, :126)
         n_methyl, P_on = self.receptor['n_methyl'], self.receptor['chemoreceptor_activity']
         delta, self.steady_iterations = 1, 0

@@ -35,7 +35,7 @@ EXPORTS = (
     'vk_exchange_ordered', 'vk_contact_scratch_bytes', 'vk_contact_step',
     'vk_response_begin', 'vk_response_end', 'vk_response_cells', 'vk_exchange_ordered_mixed',
     'vk_exchange_atomic_f64', 'vk_population_scratch_bytes', 'vk_population_plan', 'vk_contact_step_channels',
-    'vk_flagella_step',
+    'vk_flagella_step', 'vk_flagella_counts', 'vk_divide_flagella',
 )
 
 VK_CELL_MASS, VK_CELL_VOLUME, VK_CELL_LENGTH, VK_CELL_SURFACE_AREA, VK_CELL_PROTEIN, VK_CELL_ANGLE = range(6)
@@ -47,6 +47,8 @@ VK_FLAG_CHEY, VK_FLAG_CHEY_P, VK_FLAG_CW_BIAS, VK_FLAG_MOTILE_STATE, VK_FLAG_PMF
 VK_FLAG_ROWS = 5
 VK_FLAGI_TARGET, VK_FLAGI_HAVE, VK_FLAGI_MASK = range(3)
 VK_FLAGI_ROWS = 3
+VK_FLAGELLA_MERGED, VK_FLAGELLA_SPLIT_DICT = 0, 1
+VK_DIVIDE_FLAGELLA_DOMAIN = 0x666c6167656c6c61     # mixed into the seed of vk_divide_flagella's draw
 VK_GROWTH_PROTEIN, VK_GROWTH_MASS = 0, 1
 VK_RNG_STREAM, VK_RNG_PHILOX = 0, 1
 VK_DIVIDE_SET, VK_DIVIDE_SPLIT, VK_DIVIDE_ZERO = 0, 1, 2
@@ -176,6 +178,9 @@ _SIGS = {
                           _f64, _f64, _vp, _vp, _vp, _vp], ctypes.c_int),
     'vk_flagella_step': ([ctypes.POINTER(VkMotilityParams), ctypes.POINTER(VkFlagellaParams), _i64, _i64, _f64, _i32,
                           _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f64, _f64, _vp, _vp, _vp, _vp], ctypes.c_int),
+    'vk_flagella_counts': ([_i64, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+    'vk_divide_flagella': ([_i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32,
+                            ctypes.c_uint64, ctypes.c_uint64, _i64, _vp], ctypes.c_int),
     'vk_occupancy_scratch_bytes': ([_i64], ctypes.c_int64),
     'vk_occupancy_sort': ([_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp], ctypes.c_int),
     'vk_exchange_ordered': ([_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _f64, _vp], ctypes.c_int),
