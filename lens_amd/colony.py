@@ -77,7 +77,7 @@ from lens_amd.cells import CellModel, lineage_ids
 from lens_amd.configs import initial_conc
 from lens_amd.expression import ExpressionEngine
 from lens_amd.kinetics import KineticsEngine
-from lens_amd.lattice import Lattice, occupancy, segment_index, N_A_LEGACY
+from lens_amd.lattice import Lattice, occupancy, segment_index, whole_plane, N_A_LEGACY
 from lens_amd.mechanics import ContactBuffers, ContactModel, contact_step
 from lens_amd.motility import (DeviceOccupancy, DIVISION_MODES, MotilityModel, ROW_NAMES as MOTIL_ROW_NAMES, FLAG_ROW_NAMES,
                                FLAGI_ROW_NAMES, check_flagella_counts, flagella_step, motility_step)
@@ -90,7 +90,46 @@ def mmol_to_counts_from_mass(mass_fg, density_g_per_L=1100.0, avogadro=N_A_LEGAC
     return avogadro * (mass_fg / density_g_per_L * 1e-15) * 1e-3
 
 
+_SET, _SPLIT, _ZERO = native.VK_DIVIDE_SET, native.VK_DIVIDE_SPLIT, native.VK_DIVIDE_ZERO
+
+# Every per-agent array (agent = column; the last dimension is the capacity ``ld``), in the
+# order agent_array_names() reports, with its divider: what each daughter gets of the
+# mother's value.  A vk_divide_gather mode, or row ranges (lo, hi, mode) of one, or the name
+# of a divider with a launch of its own (Colony._regather).  A colony has an array if and
+# only if the attribute is a tensor.  A new per-agent array is one row here.
+AGENT_ARRAYS = (
+    ('params', _SET), ('conc', _SET), ('m2c', _SET), ('flux', _SET), ('counts', _SET), ('status', _SET),
+    ('nsteps', _SET), ('h_state', _SET),
+    ('location', 'locations'),           # daughters along the mother's angle (vk_divide_locations)
+    ('cell', ((0, native.VK_CELL_ANGLE, _SPLIT), (native.VK_CELL_ANGLE, native.VK_CELL_ROWS, _SET))),
+    ('divide', _ZERO),
+    ('lin_root', 'lineage'), ('lin_depth', 'lineage'), ('lin_path', 'lineage'),      # vk_divide_lineage
+    # 'dead' has no divider in the reference (both daughters inherit it); the daughters'
+    # processes are generated anew, so they are not frozen
+    ('dead', _SET), ('frozen', _ZERO),
+    # the receptor's and the motor's scalars, PMF and the expression's concentrations have
+    # no divider either.  The flagella count is split, the flagella go by the model's
+    # ``division`` mode, daughters get fresh keys (vk_divide_flagella)
+    ('motil', _SET), ('flag', _SET), ('flag_int', 'flagella'), ('flag_expr', _SET), ('motile_key', 'flagella'),
+    ('mech_angle', _SET),
+    ('ordinal', 'given'),                # the router's global order, computed by a collective
+    ('env_fields', _SET),                # NonSpatialEnvironment: each agent's own 1x1 field
+)
+# Tensors sized by the capacity that are not per-agent state: Colony._capacity_scratch
+# allocates them (the first row) or drops them for their users to allocate again (the second)
+CAPACITY_SCRATCH = ('bin_lin', 'bin_ix', 'env_bins', 'outflow', '_flag_expr_update',
+                    '_counts_alt', 'flux_steps', 'counts_steps', 'nsteps_steps')
+
+
 class Colony:
+    # optional state that a colony may never get (and that objects made by Colony.__new__ lack)
+    location = ordinal = env_fields = None       # set with a lattice / by the router / nonspatial
+    agent_order = None       # sort_by_bin: the reference index of the agent in each column
+    attempts = None          # count_attempts
+    _flag_expression = _flag_flags = None        # FlagellaModel(expression=...)
+    _x_stream = _p_stream = None                 # capture(overlap=True)
+    _counts_alt = flux_steps = counts_steps = nsteps_steps = None    # capture(overlap=True), step_many
+
     def __init__(self, config, n_agents: int, *, capacity: Optional[int] = None, device=None,
                  integrator: str = 'dopri5', rtol: float = 1e-8, atol: float = 1e-12,
                  max_steps: int = 100000, environment='held', env_volume_L: float = 1e-14,
@@ -111,7 +150,7 @@ class Colony:
             if motility.ligand_id not in environment.molecules:
                 raise ValueError('motility: the lattice has no %r plane (molecules: %s)' % (
                     motility.ligand_id, environment.molecules))
-            if environment.pad_top or environment.pad_bot or not (environment.edge_top and environment.edge_bot):
+            if not whole_plane(environment):
                 raise ValueError('motility needs a whole, unbanded plane (row bands are not supported)')
             if cells is not None and motility.division is None:
                 # the model must say how the motile state divides (MotilityModel(division=...))
@@ -121,7 +160,7 @@ class Colony:
             # re-bins the agents on the device, on one whole plane
             if not isinstance(environment, Lattice):
                 raise ValueError('mechanics needs a Lattice environment (capsules move on its plane)')
-            if environment.pad_top or environment.pad_bot or not (environment.edge_top and environment.edge_bot):
+            if not whole_plane(environment):
                 raise ValueError('mechanics needs a whole, unbanded plane (row bands are not supported)')
             if motility is not None:
                 raise ValueError('mechanics with motility is not supported (two writers of position and heading)')
@@ -145,7 +184,7 @@ class Colony:
             if motility is not None:
                 raise ValueError('response with motility is not supported')
             if isinstance(environment, Lattice):
-                if environment.pad_top or environment.pad_bot or not (environment.edge_top and environment.edge_bot):
+                if not whole_plane(environment):
                     raise ValueError('response needs a whole, unbanded plane (row bands are not supported)')
                 for mol in (response.membrane or {}).get('molecules_to_diffuse', []):
                     if mol not in environment.molecules:
@@ -206,12 +245,9 @@ class Colony:
         self.h_state = z(ld)
         self.time = 0.0
         self.step_index = 0
-        self._layout = 0             # bumped when step buffers are reallocated (Colony.capture checks it)
+        self._layout = 0             # bumped when buffers are reallocated (Colony.capture checks it)
         self.lattice: Optional[Lattice] = None
         self.router = None       # distributed.AgentRouter (row-banded multi-rank lattice colonies)
-        self.ordinal = None      # global single-rank-order key (set by the router)
-        self.location = None
-        self.env_fields = None
         self.cells = cells
         self.motility = motility
         self.mechanics = mechanics
@@ -239,14 +275,11 @@ class Colony:
             self.lattice = environment
             self._setup_maps(self.lattice.molecules)
             self.location = z(2, ld)
-            self.bin_lin = z(ld, dtype=torch.int32)
-            self.bin_ix = z(ld, dtype=torch.int32)
             if motility is not None:
                 self.motil = torch.from_numpy(motility.initial_rows(self.n, ld)).to(dev).contiguous()
                 # global inner-update index of the next motility launch (the Philox counter
                 # word): on the device, advanced by each launch, so graphs replay it
                 self._motil_counter = z(1, dtype=torch.int64)
-                self._occ_dev = DeviceOccupancy(ld, dev)
                 if motility.flagella is not None:
                     # the multi-flagellar motor's state: FP64 rows, and count / count / mask
                     flag, flag_int = motility.flagella.initial_rows(self.n, ld, motility.seed)
@@ -266,13 +299,10 @@ class Colony:
                     self.flag_expr = torch.from_numpy(np.ascontiguousarray(
                         np.repeat(fm.expression_initial[:, None], ld, axis=1))).to(dev).contiguous()
                     self._flag_expression = ExpressionEngine(fm.expression_table, dev)
-                    self._flag_expr_update = z(len(fm.expression_table.outputs), ld)
                     self._flag_flags = z(1, dtype=torch.int32)
                     self._flagella_counts()
-            if mechanics is not None:
-                if cells is None:
-                    self.mech_angle = torch.from_numpy(mechanics.initial_angles(self.n, ld)).to(dev).contiguous()
-                self._mech_buffers()
+            if mechanics is not None and cells is None:
+                self.mech_angle = torch.from_numpy(mechanics.initial_angles(self.n, ld)).to(dev).contiguous()
         elif environment == 'nonspatial':
             mols = []
             extra = self._resp_layout.molecules if response is not None else []
@@ -285,16 +315,51 @@ class Colony:
             depth_um = env_volume_L * 1e15                     # V / (1 um * 1 um)
             bin_volume = (depth_um * 1.0 * 1.0) * 1e-15 / 1    # get_bin_volume([1,1],[1,1],depth)
             self.env_binvol_avogadro = bin_volume * avogadro
-            self.env_bins = torch.arange(ld, dtype=torch.int32, device=dev)
-            self._env_to_external()          # derivers run once at t = 0
         elif environment != 'held':
             raise ValueError('environment must be held, nonspatial or a Lattice')
-        if response is not None:
-            self._response_buffers()
-            if self.lattice is not None and exchange == 'sorted':
-                # the occupancy of the initial bins (set_agents(location=...) rebuilds it)
-                lat = self.lattice
-                self._occ_dev.sort(self.bin_lin, self.n, lat.rows_local * lat.ny, None)
+        self._capacity_scratch()
+        if self.env_fields is not None:
+            self._env_to_external()          # derivers run once at t = 0
+        if response is not None and self.lattice is not None and exchange == 'sorted':
+            # the occupancy of the initial bins (set_agents(location=...) rebuilds it)
+            lat = self.lattice
+            self._occ_dev.sort(self.bin_lin, self.n, lat.rows_local * lat.ny, None)
+
+    def _capacity_scratch(self):
+        """Everything sized by the capacity that is not per-agent state (CAPACITY_SCRATCH and
+        the buffer objects), for the current ``ld``: the only place that allocates it.  Called
+        by the constructor and whenever ``ld`` changes, by division or by
+        distributed.install_agents; captured graphs hold the old buffers, so ``_layout`` moves."""
+        ld, dev, lat = self.ld, self.device, self.lattice
+        i32 = lambda: torch.zeros(ld, dtype=torch.int32, device=dev)
+        if lat is not None:
+            self.bin_lin, self.bin_ix = i32(), i32()
+            if self.motility is not None or self.mechanics is not None or self.response is not None:
+                # these colonies exchange in agent order through an occupancy built on the device
+                self._occ_dev = DeviceOccupancy(ld, dev)
+        if self.env_fields is not None:
+            self.env_bins = torch.arange(ld, dtype=torch.int32, device=dev)     # agent a owns bin a
+        if self.mechanics is not None:
+            # the contact launch's scratch; its counter and flag word are not per agent and carry over
+            gx, gy = self.mechanics.grid(lat.bounds)
+            old = getattr(self, '_mech', None)
+            self._mech = ContactBuffers(ld, gx * gy, dev)
+            if old is not None:
+                self._mech.counter.copy_(old.counter)
+                self._mech.flags.copy_(old.flags)
+            if self.mechanics.channels is not None:
+                # the mother machine's outflow flags: written by every contact launch, read at
+                # the end of the step
+                self.outflow = i32()
+        if self.response is not None:
+            self._resp_buf = ResponseBuffers(self._resp_layout, ld, self.table.n_reactions, dev,
+                                             self.cells is not None)
+        if self._flag_expression is not None:
+            self._flag_expr_update = torch.zeros((len(self._flag_expression.table.outputs), ld),
+                                                 dtype=torch.float64, device=dev)
+        # sized by ld too, allocated by their users (capture(overlap=True), step_many)
+        self._counts_alt = self.flux_steps = self.counts_steps = self.nsteps_steps = None
+        self._layout += 1
 
     # -- maps between SoA rows and field planes ---------------------------------
     def _setup_maps(self, molecules):
@@ -380,30 +445,9 @@ class Colony:
             row.copy_(torch.from_numpy(c[:self.n].astype(np.int32)))
 
     def agent_array_names(self):
-        """Every per-agent array (agent = column), as attribute names: what
-        division gathers and the router migrates."""
-        names = ['params', 'conc', 'm2c', 'flux', 'counts', 'status', 'nsteps', 'h_state']
-        if self.location is not None:
-            names.append('location')
-        if self.cells is not None:
-            names += ['cell', 'divide', 'lin_root', 'lin_depth', 'lin_path']
-        if getattr(self, 'response', None) is not None:
-            names += ['dead', 'frozen']
-        if getattr(self, 'motility', None) is not None:
-            names.append('motil')
-            if self.motility.flagella is not None:
-                names += ['flag', 'flag_int']
-                if self.motility.flagella.expression is not None:
-                    names.append('flag_expr')
-            if self.cells is not None:
-                names.append('motile_key')
-        if getattr(self, 'mechanics', None) is not None and self.cells is None:
-            names.append('mech_angle')
-        if self.ordinal is not None:
-            names.append('ordinal')
-        if self.env_fields is not None:
-            names.append('env_fields')      # NonSpatialEnvironment: each agent's own 1x1 field
-        return names
+        """Every per-agent array this colony has (agent = column), as attribute names in
+        the order of AGENT_ARRAYS: what division gathers and the router migrates."""
+        return [name for name, _ in AGENT_ARRAYS if torch.is_tensor(getattr(self, name, None))]
 
     def refresh_bins(self):
         """Recompute bin sites and the agent-ordered bin occupancy (after moves).
@@ -417,10 +461,10 @@ class Colony:
         if self.n and (int(ix.min()) < lat.row_lo_global or int(ix.max()) >= lat.row_hi_global):
             raise ValueError('agents outside this rank\'s row band: attach a distributed.AgentRouter '
                              '(division moves daughters across band edges)')
-        self.occ = occupancy(self.bin_lin, self.n, getattr(self, 'agent_order', None))
+        self.occ = occupancy(self.bin_lin, self.n, self.agent_order)
         if self.response is not None and self.exchange_mode == 'sorted':
             # a response colony exchanges through the device occupancy: one ordered kernel
-            self._occ_dev.sort(self.bin_lin, self.n, lat.rows_local * lat.ny, getattr(self, 'agent_order', None))
+            self._occ_dev.sort(self.bin_lin, self.n, lat.rows_local * lat.ny, self.agent_order)
         self._update_coupling()
         self._layout += 1            # captured graphs hold the old occupancy buffers
 
@@ -436,12 +480,12 @@ class Colony:
             return      # agents leave bin order every step: the separate launches
         if self.response is not None:
             return      # the mixed exchange is its own launch
-        if lat.pad_top or lat.pad_bot or not (lat.edge_top and lat.edge_bot):
+        if not whole_plane(lat):
             return
         # stored in bin order, and within a bin in the exchange's agent order
         # (occupancy: agent_order after sort_by_bin, else the column order)
         b = self.bin_lin[:n].to(torch.int64)
-        key = getattr(self, 'agent_order', None)
+        key = self.agent_order
         if n > 1:
             same = b[1:] == b[:-1]
             ok = (b[1:] > b[:-1]) | (same & (key[1:n] > key[:n - 1]) if key is not None else same)
@@ -476,7 +520,7 @@ class Colony:
         if self.cells is not None or self.router is not None:
             raise ValueError('sort_by_bin: division and routed bands keep the reference agent order')
         n = self.n
-        prev = getattr(self, 'agent_order', None)
+        prev = self.agent_order
         key = prev if prev is not None else torch.arange(n, dtype=torch.int64, device=self.device)
         by_key = torch.sort(key[:n], stable=True).indices
         perm = by_key[torch.sort(self.bin_lin[:n].to(torch.int64)[by_key], stable=True).indices]
@@ -509,7 +553,7 @@ class Colony:
         self.engine.dopri5_gather(dt, self.params, self.conc, self.m2c, self.n, self.h_state, self.rtol, self.atol,
                                   self.max_steps, self.flux, self.counts, self.status, self.nsteps, lat.fields,
                                   lat.field_stride, self.bin_lin, self.map_gather_field, self.map_gather_row)
-        if getattr(self, 'attempts', None) is not None:
+        if self.attempts is not None:
             self.attempts += self.nsteps[:self.n].sum()
 
     def gather_external(self):
@@ -545,12 +589,12 @@ class Colony:
             self.engine.dopri5(dt, self.params, self._kin_conc(), self.m2c, self.n, self.h_state, self.rtol,
                                self.atol, self.max_steps, self.flux, self.counts, self.status,
                                self.nsteps)
-            if getattr(self, 'attempts', None) is not None:
+            if self.attempts is not None:
                 self.attempts += self.nsteps[:self.n].sum()
 
     def _step_buffers(self, k):
         t, ld = self.table, self.ld
-        if getattr(self, 'flux_steps', None) is None or self.flux_steps.shape[0] != k:
+        if self.flux_steps is None or self.flux_steps.shape[0] != k:
             self.flux_steps = torch.zeros((k, t.n_reactions, ld), dtype=torch.float64, device=self.device)
             self.counts_steps = torch.zeros((k, t.n_ext, ld), dtype=torch.int64, device=self.device)
             self.nsteps_steps = torch.zeros((k, ld), dtype=torch.int32, device=self.device)
@@ -574,7 +618,7 @@ class Colony:
                                  self.atol, self.max_steps, self.flux_steps, self.counts_steps, self.status,
                                  self.nsteps_steps)
         self.flux, self.counts, self.nsteps = self.flux_steps[k - 1], self.counts_steps[k - 1], self.nsteps_steps[k - 1]
-        if getattr(self, 'attempts', None) is not None:
+        if self.attempts is not None:
             self.attempts += self.nsteps_steps[:, :self.n].sum()
         self.time += dt * k
         self.step_index += k
@@ -782,7 +826,7 @@ class Colony:
             raise ValueError('a motile colony takes no router')
         # a dividing colony draws by the agent's own key; its column order is the reference's
         # agent order, which the occupancy below keeps (key None)
-        key = self.motile_key if self.cells is not None else getattr(self, 'agent_order', None)
+        key = self.motile_key if self.cells is not None else self.agent_order
         if self.motility.flagella is not None:
             flagella_step(self.motility, self.lattice, self.location, self.motil, self.flag, self.flag_int, self.n,
                           dt, self._motil_counter, key=key, bin_lin=self.bin_lin, bin_ix=self.bin_ix)
@@ -794,22 +838,7 @@ class Colony:
             self.cell[native.VK_CELL_ANGLE, :self.n].copy_(self.motil[native.VK_MOTIL_ANGLE, :self.n])
         if self.exchange_mode == 'sorted' and self.map_exch_count.numel():
             lat = self.lattice
-            self._occ_dev.sort(self.bin_lin, self.n, lat.rows_local * lat.ny, getattr(self, 'agent_order', None))
-
-    def _mech_buffers(self):
-        """The device occupancy and the contact launch's scratch, counter and flag word
-        for ``ld`` agents (again when division grows ``ld``: the counter carries over)."""
-        gx, gy = self.mechanics.grid(self.lattice.bounds)
-        old = getattr(self, '_mech', None)
-        self._occ_dev = DeviceOccupancy(self.ld, self.device)
-        self._mech = ContactBuffers(self.ld, gx * gy, self.device)
-        if self.mechanics.channels is not None:
-            # the mother machine's outflow flags: written by every contact launch, read at
-            # the end of the step
-            self.outflow = torch.zeros(self.ld, dtype=torch.int32, device=self.device)
-        if old is not None:
-            self._mech.counter.copy_(old.counter)
-            self._mech.flags.copy_(old.flags)
+            self._occ_dev.sort(self.bin_lin, self.n, lat.rows_local * lat.ny, self.agent_order)
 
     def _mechanics_step(self):
         """First in the step of a colony with mechanics: the contact relaxation
@@ -822,7 +851,7 @@ class Colony:
             angle, length = self.cell[native.VK_CELL_ANGLE], self.cell[native.VK_CELL_LENGTH]
         else:
             angle, length = self.mech_angle, None
-        key = getattr(self, 'agent_order', None)
+        key = self.agent_order
         contact_step(self.mechanics, self.lattice, self.location, angle, self.n, self._mech, length=length,
                      key=key, bin_lin=self.bin_lin, bin_ix=self.bin_ix,
                      outflow=self.outflow if self.mechanics.channels is not None else None)
@@ -831,14 +860,6 @@ class Colony:
             self._occ_dev.sort(self.bin_lin, self.n, lat.rows_local * lat.ny, key)
 
     # -- the antibiotic response (lens_amd/response.py) ----------------------------
-    def _response_buffers(self):
-        """The response's per-agent scratch for ``ld`` agents, and the device occupancy of
-        the ordered exchange (again when division grows ``ld``)."""
-        self._resp_buf = ResponseBuffers(self._resp_layout, self.ld, self.table.n_reactions, self.device,
-                                         self.cells is not None)
-        if self.lattice is not None and self.mechanics is None:
-            self._occ_dev = DeviceOccupancy(self.ld, self.device)
-
     def _response_begin(self, dt):
         """Before the kinetics launch, all from the step-start state: the detector, the
         membrane terms, the frozen agents' saved columns, the expression update."""
@@ -890,7 +911,7 @@ class Colony:
         passes) waits for the previous exchange, so each step sees exactly the state a
         sequential step would."""
         lat = self.lattice
-        if getattr(self, '_x_stream', None) is None:
+        if self._x_stream is None:
             self._x_stream = torch.cuda.Stream(self.device)
             self._p_stream = torch.cuda.Stream(self.device)
         sx, sp = self._x_stream, self._p_stream
@@ -962,8 +983,7 @@ class Colony:
             raise ValueError('Colony.capture: a colony with channels removes its outflow on the host every step '
                              '(the agent count changes) and cannot be replayed from one graph')
         lat = self.lattice
-        if (self.cells is not None or self.environment == 'nonspatial' or
-                (lat is not None and (lat.pad_top or lat.pad_bot or not (lat.edge_top and lat.edge_bot)))):
+        if self.cells is not None or self.environment == 'nonspatial' or (lat is not None and not whole_plane(lat)):
             raise ValueError('Colony.capture: division, row bands and NonSpatialEnvironment take host decisions '
                              'per step and cannot be replayed from one graph (a row band: capture_banded)')
         if steps < 1:
@@ -982,7 +1002,7 @@ class Colony:
         if overlap and self.response is not None:
             raise ValueError('Colony.capture: overlap is not available for a colony with a response')
         overlap = bool(overlap) and self._overlap_ok() and spl == 1
-        if overlap and (getattr(self, '_counts_alt', None) is None or self._counts_alt.shape != self.counts.shape):
+        if overlap and (self._counts_alt is None or self._counts_alt.shape != self.counts.shape):
             self._counts_alt = torch.zeros_like(self.counts)
         counts0 = self.counts
         graph = torch.cuda.CUDAGraph()
@@ -1125,12 +1145,12 @@ class Colony:
     def _flagella_check(self):
         """Raises if a derived flagella count ever left 0..32 (one host read: called where
         the host reads from the device anyway)."""
-        if getattr(self, '_flag_flags', None) is not None and int(self._flag_flags.item()):
+        if self._flag_flags is not None and int(self._flag_flags.item()):
             raise FloatingPointError('a derived flagella count left 0..32 (concentration * mmol_to_counts was '
                                      'negative, not a number or 33 and more): the motor holds 32 flagella')
 
     def _finish_step(self, dt):
-        if self.motility is not None and getattr(self, 'flag_expr', None) is not None:
+        if self._flag_expression is not None:
             # the expression process from the step-start state (ode_expression.py:265-303), then
             # its counts deriver -- in front of DeriveGlobals (core/process.py:75-103), so with
             # the mmol_to_counts the previous step left; both before vk_cell_step touches m2c
@@ -1233,8 +1253,7 @@ class Colony:
         occupancies are rebuilt as after a division.  Returns the number removed (one
         host read).  ``col.remove(col.dead[:col.n] != 0)`` drops a response colony's dead."""
         lat = self.lattice
-        if self.router is not None or (lat is not None and (
-                lat.pad_top or lat.pad_bot or not (lat.edge_top and lat.edge_bot))):
+        if self.router is not None or (lat is not None and not whole_plane(lat)):
             raise ValueError('Colony.remove: a colony with a router or a banded lattice keeps its agents '
                              '(their global order lives on other ranks)')
         n, ld, dev, st = self.n, self.ld, self.device, native.stream_handle()
@@ -1254,132 +1273,94 @@ class Colony:
         n_out = int(n_out_dev.item())
         if n_out == n:
             return 0
-        names = self.agent_array_names()
-        if getattr(self, 'agent_order', None) is not None:
-            names.append('agent_order')
-        for name in names:
-            t = getattr(self, name)
-            if not t.is_contiguous():        # flux / counts / nsteps may view step_many's buffers
-                t = t.contiguous()
-            rows = 1 if t.dim() == 1 else t.shape[0]
-            ld_src = t.shape[-1]
-            ld_dst = ld if ld_src == ld else n_out      # agent_order holds n keys, not ld
-            out = torch.zeros(t.shape[:-1] + (ld_dst,), dtype=t.dtype, device=dev)
-            native.check(native._lib.vk_divide_gather(
-                n_out, native.ptr(src), native.ptr(kind), native.ptr(t), ld_src, native.ptr(out), ld_dst, rows,
-                t.element_size(), native.VK_DIVIDE_SET, st), 'vk_divide_gather(%s)' % name)
-            setattr(self, name, out)
-        self.n = n_out
-        if lat is not None:
-            self.bin_lin = torch.zeros(ld, dtype=torch.int32, device=dev)
-            self.bin_ix = torch.zeros(ld, dtype=torch.int32, device=dev)
-            self.refresh_bins()          # bins, host and device occupancy, the _layout bump
-        else:
-            self._layout += 1
+        self._regather(n_out, src, kind, ld, declared=False)
         return n - n_out
 
     def _apply_division(self, n_out, src, kind, ordinal=None):
         if self.motility is not None and self._key_base + 2 * (n_out - self.n) - 1 > 2 ** 31 - 1:
             # before any array is gathered into the new layout
             raise OverflowError('a motility key would pass 2**31 - 1 (the kernels put it into a 32-bit counter word)')
-        ld_src = self.ld
-        ld = max(self.ld, n_out)
-        if n_out > self.ld:
-            ld = max(n_out, int(self.ld * 1.25) + 64)
-        dev, st = self.device, native.stream_handle()
-        S, SP, Z = native.VK_DIVIDE_SET, native.VK_DIVIDE_SPLIT, native.VK_DIVIDE_ZERO
-
-        def gather(t, divider=S, rows_slice=None):
-            rows = 1 if t.dim() == 1 else t.shape[0]
-            out = torch.empty((ld,) if t.dim() == 1 else (rows, ld), dtype=t.dtype, device=dev)
-            native.check(native._lib.vk_divide_gather(
-                n_out, native.ptr(src), native.ptr(kind), native.ptr(t), ld_src, native.ptr(out), ld, rows,
-                t.element_size(), divider, st), 'vk_divide_gather')
-            return out
-
-        for name in ('params', 'conc', 'm2c', 'flux', 'counts', 'status', 'nsteps', 'h_state'):
-            setattr(self, name, gather(getattr(self, name)))
-        if self.env_fields is not None:
-            self.env_fields = gather(self.env_fields)
-            self.env_bins = torch.arange(ld, dtype=torch.int32, device=dev)
-        cell = torch.empty((native.VK_CELL_ROWS, ld), dtype=torch.float64, device=dev)
-        n_split = native.VK_CELL_ANGLE      # rows [0, angle) split, angle copied
-        native.check(native._lib.vk_divide_gather(
-            n_out, native.ptr(src), native.ptr(kind), native.ptr(self.cell), ld_src, native.ptr(cell), ld,
-            n_split, 8, SP, st), 'vk_divide_gather(cell)')
-        native.check(native._lib.vk_divide_gather(
-            n_out, native.ptr(src), native.ptr(kind), self.cell.data_ptr() + n_split * ld_src * 8, ld_src,
-            cell.data_ptr() + n_split * ld * 8, ld, native.VK_CELL_ROWS - n_split, 8, S, st),
-            'vk_divide_gather(angle)')
-        self.divide = gather(self.divide, Z)
-        if self.response is not None:
-            # 'dead' has no divider (the set divider: both daughters inherit it); the
-            # daughters' processes are generated anew, so they are not frozen
-            self.dead = gather(self.dead)
-            self.frozen = gather(self.frozen, Z)
-        if self.motility is not None:
-            self._divide_motile(n_out, src, kind, ld_src, ld, gather)
-        root = torch.empty(ld, dtype=torch.int32, device=dev)
-        depth = torch.empty(ld, dtype=torch.int32, device=dev)
-        path = torch.empty(ld, dtype=torch.int64, device=dev)
-        native.check(native._lib.vk_divide_lineage(
-            n_out, native.ptr(src), native.ptr(kind), native.ptr(self.lin_root), native.ptr(self.lin_depth),
-            native.ptr(self.lin_path), native.ptr(root), native.ptr(depth), native.ptr(path),
-            native.ptr(self._overflow), st), 'vk_divide_lineage')
-        if self.location is not None:
-            loc = torch.empty((2, ld), dtype=torch.float64, device=dev)
-            native.check(native._lib.vk_divide_locations(
-                n_out, native.ptr(src), native.ptr(kind), native.ptr(self.location), ld_src, native.ptr(loc), ld,
-                native.ptr(cell), st), 'vk_divide_locations')
-            self.location = loc
-        self.cell, self.lin_root, self.lin_depth, self.lin_path = cell, root, depth, path
-        if ordinal is not None:
-            self.ordinal = torch.zeros(ld, dtype=torch.int64, device=dev)
-            self.ordinal[:n_out] = ordinal
-        self.n, self.ld = n_out, ld
-        if self.mechanics is not None and ld != ld_src:
-            self._mech_buffers()
-        if self.response is not None and ld != ld_src:
-            self._response_buffers()
-        if self.motility is not None and ld != ld_src:
-            # the occupancy buffers for the new capacity; the Philox counter is not per agent
-            self._occ_dev = DeviceOccupancy(ld, dev)
-            if getattr(self, 'flag_expr', None) is not None:
-                self._flag_expr_update = torch.zeros((self._flag_expr_update.shape[0], ld), dtype=torch.float64,
-                                                     device=dev)
-        if self.lattice is not None:
-            self.bin_lin = torch.zeros(ld, dtype=torch.int32, device=dev)
-            self.bin_ix = torch.zeros(ld, dtype=torch.int32, device=dev)
-            self.refresh_bins()
+        ld = self.ld if n_out <= self.ld else max(n_out, int(self.ld * 1.25) + 64)
+        self._regather(n_out, src, kind, ld, ordinal=ordinal)
         if int(self._overflow.item()):
             raise OverflowError('a lineage exceeded 64 generations (phylogeny path bits)')
 
-    def _divide_motile(self, n_out, src, kind, ld_src, ld, gather):
-        """The motile state's dividers (called by _apply_division before the lineage arrays
-        are replaced: the split's draw is keyed by the mother's lineage).  The receptor's and
-        the motor's scalars, PMF and the expression's concentrations have no divider: both
-        daughters start with the mother's value.  The flagella count is split, the flagella
-        go by the model's ``division`` mode, daughters get fresh keys (vk_divide_flagella)."""
-        m, dev = self.motility, self.device
-        n_daughters = 2 * (n_out - self.n)           # vk_divide_plan: nobody is removed
-        self.motil = gather(self.motil)
-        flag_int = None
-        if m.flagella is not None:
-            self.flag = gather(self.flag)
-            if getattr(self, 'flag_expr', None) is not None:
-                self.flag_expr = gather(self.flag_expr)
-            flag_int = torch.empty((native.VK_FLAGI_ROWS, ld), dtype=torch.int32, device=dev)
-        key = torch.empty(ld, dtype=torch.int64, device=dev)
-        native.check(native._lib.vk_divide_flagella(
-            n_out, n_out - n_daughters, self.n, native.ptr(src), native.ptr(kind),
-            native.ptr(self.flag_int) if flag_int is not None else 0, ld_src, native.ptr(self.motile_key),
-            native.ptr(self.lin_root), native.ptr(self.lin_depth), native.ptr(self.lin_path), native.ptr(flag_int), ld,
-            native.ptr(key), DIVISION_MODES[m.division], m.seed & (2 ** 64 - 1), self.step_index & (2 ** 64 - 1),
-            self._key_base, native.stream_handle()), 'vk_divide_flagella')
-        if flag_int is not None:
-            self.flag_int = flag_int
-        self.motile_key = key
-        self._key_base += n_daughters
+    def _regather(self, n_out, src, kind, ld, declared=True, ordinal=None):
+        """Every per-agent array gathered once by a plan (``src`` / ``kind`` of vk_divide_plan
+        or vk_population_plan, ``n_out`` agents) into capacity ``ld``: each with the divider
+        AGENT_ARRAYS declares into uninitialised arrays (division), or, ``declared=False``,
+        all with the set divider into zero-filled ones (removal: the plan holds no daughters;
+        ``agent_order`` is compacted to its ``n_out`` keys).  Only the old arrays are read;
+        the new ones are installed together, then the scratch follows the capacity and the
+        bins and occupancies are rebuilt."""
+        dev, st, n, ld_src = self.device, native.stream_handle(), self.n, self.ld
+        alloc = torch.empty if declared else torch.zeros
+        plan = (n_out, native.ptr(src), native.ptr(kind))
+        new = {}
+
+        def gather(name, t, ld_dst, ranges):
+            t = t.contiguous()               # flux / counts / nsteps may view step_many's buffers
+            out = alloc(t.shape[:-1] + (ld_dst,), dtype=t.dtype, device=dev)
+            size, ld_t = t.element_size(), t.shape[-1]
+            for lo, hi, mode in ranges:
+                rows = 1 if t.dim() == 1 else (t.shape[0] if hi is None else hi) - lo
+                native.check(native._lib.vk_divide_gather(
+                    *plan, t.data_ptr() + lo * ld_t * size, ld_t, out.data_ptr() + lo * ld_dst * size, ld_dst, rows,
+                    size, mode, st), 'vk_divide_gather(%s)' % name)
+            return out
+
+        old = {name: getattr(self, name) for name in self.agent_array_names()}
+        for name, divider in AGENT_ARRAYS:
+            if name not in old:
+                continue
+            if not declared:
+                divider = _SET
+            if isinstance(divider, int):
+                divider = ((0, None, divider),)          # every row
+            if isinstance(divider, tuple):
+                new[name] = gather(name, old[name], ld, divider)
+            elif divider == 'given':
+                new[name] = torch.zeros(ld, dtype=torch.int64, device=dev)
+                new[name][:n_out] = ordinal
+        if not declared and self.agent_order is not None:
+            new['agent_order'] = gather('agent_order', self.agent_order, n_out, ((0, None, _SET),))
+        if declared:
+            # the dividers with a launch of their own: each writes several arrays, or reads a gathered one
+            empty = lambda like: torch.empty(like.shape[:-1] + (ld,), dtype=like.dtype, device=dev)
+            lineage = [old[name] for name in ('lin_root', 'lin_depth', 'lin_path')]
+            new.update({name: empty(old[name]) for name in ('lin_root', 'lin_depth', 'lin_path')})
+            native.check(native._lib.vk_divide_lineage(
+                *plan, *map(native.ptr, lineage), native.ptr(new['lin_root']), native.ptr(new['lin_depth']),
+                native.ptr(new['lin_path']), native.ptr(self._overflow), st), 'vk_divide_lineage')
+            if 'location' in old:
+                # along the mother's angle, by a quarter of the length she had: the gathered cell rows
+                new['location'] = empty(old['location'])
+                native.check(native._lib.vk_divide_locations(
+                    *plan, native.ptr(old['location']), ld_src, native.ptr(new['location']), ld,
+                    native.ptr(new['cell']), st), 'vk_divide_locations')
+            if 'motile_key' in old:
+                # the split's draw is keyed by the mother's lineage; a colony on the coarse motor
+                # has no flagella and gets keys only
+                m, n_daughters = self.motility, 2 * (n_out - n)      # vk_divide_plan: nobody is removed
+                new['motile_key'] = empty(old['motile_key'])
+                if 'flag_int' in old:
+                    new['flag_int'] = empty(old['flag_int'])
+                native.check(native._lib.vk_divide_flagella(
+                    n_out, n_out - n_daughters, n, native.ptr(src), native.ptr(kind), native.ptr(old.get('flag_int')),
+                    ld_src, native.ptr(old['motile_key']), *map(native.ptr, lineage), native.ptr(new.get('flag_int')),
+                    ld, native.ptr(new['motile_key']), DIVISION_MODES[m.division], m.seed & (2 ** 64 - 1),
+                    self.step_index & (2 ** 64 - 1), self._key_base, st), 'vk_divide_flagella')
+                self._key_base += n_daughters
+        for name, t in new.items():
+            setattr(self, name, t)
+        self.n = n_out
+        if ld != self.ld:
+            self.ld = ld
+            self._capacity_scratch()
+        if self.lattice is not None:
+            self.refresh_bins()          # bins, host and device occupancy, the _layout bump
+        else:
+            self._layout += 1
 
     def agent_ids(self):
         """Phylogeny ids of agents 0..n-1 (meta_division.py:15-18)."""
@@ -1434,7 +1415,7 @@ class Colony:
                 out['flagella'] = {name: f[row].copy() for row, name in enumerate(FLAG_ROW_NAMES)}
                 out['flagella'].update({name: fi[row].copy() for row, name in enumerate(FLAGI_ROW_NAMES)})
                 out['flagella']['mask'] = out['flagella']['mask'].view(np.uint32)     # bit i: flagellum i is CW
-                if getattr(self, 'flag_expr', None) is not None:
+                if self._flag_expression is not None:
                     e = self.flag_expr[:, :self.n].cpu().numpy()
                     out['flagella_expression'] = {name: e[row].copy() for row, name in
                                                   enumerate(self.motility.flagella.expression_names)}

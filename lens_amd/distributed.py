@@ -148,10 +148,10 @@ class AgentRouter:
 
     def __init__(self, col, rank: int, world: int, group=None, agent_offset: int = None):
         self.col, self.rank, self.world, self.group = col, rank, world, group
-        if getattr(col, 'motility', None) is not None:
+        if col.motility is not None:
             raise ValueError('AgentRouter: a motile colony (Colony(motility=...)) takes no router: its agents '
                              'move and re-bin on one device, on a whole plane')
-        if getattr(col, 'mechanics', None) is not None:
+        if col.mechanics is not None:
             raise ValueError('AgentRouter: a colony with mechanics (Colony(mechanics=...)) takes no router: its '
                              'agents move and re-bin on one device, on a whole plane')
         lat = col.lattice
@@ -244,8 +244,6 @@ class AgentRouter:
             # immigrants merge with the stayers by ordinal
             perm = torch.sort(both['ordinal'].reshape(-1), stable=True).indices
             install_agents(col, names, {name: v.index_select(1, perm) for name, v in both.items()})
-            col.bin_lin = torch.zeros(col.ld, dtype=torch.int32, device=col.device)
-            col.bin_ix = torch.zeros(col.ld, dtype=torch.int32, device=col.device)
         return sum(recv_counts_l)
 
 
@@ -292,7 +290,7 @@ def unpack_agents(col, names, recv):
 
 def install_agents(col, names, pieces):
     """Replace every per-agent array by ``pieces[name]`` ([rows, n_new]),
-    growing the capacity when needed."""
+    growing the capacity when needed (the colony's scratch then follows it)."""
     n_new = pieces[names[0]].shape[1]
     ld = col.ld if n_new <= col.ld else max(n_new, int(col.ld * 1.25) + 64)
     for name in names:
@@ -303,10 +301,10 @@ def install_agents(col, names, pieces):
         else:
             out[:, :n_new] = pieces[name]
         setattr(col, name, out)
-    col.n, col.ld = n_new, ld
-    if getattr(col, 'env_fields', None) is not None:
-        # NonSpatialEnvironment: agent a's field is env_fields[:, a] (stride ld)
-        col.env_bins = torch.arange(ld, dtype=torch.int32, device=col.device)
+    col.n = n_new
+    if ld != col.ld:
+        col.ld = ld
+        col._capacity_scratch()
 
 
 class AgentBalancer:

@@ -35,6 +35,11 @@ def n_substeps(timestep: float, dt_max: float = 0.01) -> int:
     return n
 
 
+def whole_plane(lat) -> bool:
+    """Whether ``lat`` holds whole, unbanded planes: no halo rows and both edges its own."""
+    return not (lat.pad_top or lat.pad_bot or not (lat.edge_top and lat.edge_bot))
+
+
 def stencil_depth(k: int = 0) -> int:
     """Set (1..15 odd, or 10) / query (0) the substeps fused per HBM pass; returns the previous.
     10 plans a block of a multiple of 10 substeps as 10-deep passes (vk_diffuse; in the
@@ -243,7 +248,7 @@ class Lattice:
         single-substep pass -- vk_diffuse's planner, restated (10-deep passes in
         the tolerance mode's depth-10 setting, else odd depths); the library makes
         the same decision and launches nothing otherwise."""
-        if self.pad_top or self.pad_bot or not (self.edge_top and self.edge_bot) or len(self.molecules) > 8:
+        if not whole_plane(self) or len(self.molecules) > 8:
             return False
         n_sub = n_substeps(timestep, self.diffusion_dt)
         depth = native._lib.vk_set_stencil_depth(0)

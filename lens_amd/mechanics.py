@@ -187,7 +187,8 @@ def contact_step(model: ContactModel, lattice, location, angle, n: int, buffers:
     after an iteration, 0 for the others.  The lattice must hold whole, unbanded
     planes.  No host read."""
     import torch
-    if lattice.pad_top or lattice.pad_bot or not (lattice.edge_top and lattice.edge_bot):
+    from lens_amd.lattice import whole_plane
+    if not whole_plane(lattice):
         raise ValueError('contact_step: a whole, unbanded plane')
     ld = location.shape[1]
     for t in (angle, length):

@@ -293,7 +293,8 @@ def motility_step(model: MotilityModel, lattice, location, motil, n: int, dt: fl
     the inner-update index and is advanced.  ``bin_lin`` / ``bin_ix`` (int32
     [ld]) receive the bins.  The lattice must hold whole, unbanded planes."""
     import torch
-    if lattice.pad_top or lattice.pad_bot or not (lattice.edge_top and lattice.edge_bot):
+    from lens_amd.lattice import whole_plane
+    if not whole_plane(lattice):
         raise ValueError('motility_step: a whole, unbanded plane')
     ld = location.shape[1]
     if motil.shape != (native.VK_MOTIL_ROWS, ld) or not (motil.is_contiguous() and location.is_contiguous()):
@@ -316,9 +317,10 @@ def flagella_step(model: MotilityModel, lattice, location, motil, flag, flag_int
     ``model.flagella``'s motor in the place of the coarse one, on ``flag``
     [VK_FLAG_ROWS, ld] (float64) and ``flag_int`` [VK_FLAGI_ROWS, ld] (int32)."""
     import torch
+    from lens_amd.lattice import whole_plane
     if model.flagella is None:
         raise ValueError('flagella_step: the model has no FlagellaModel')
-    if lattice.pad_top or lattice.pad_bot or not (lattice.edge_top and lattice.edge_bot):
+    if not whole_plane(lattice):
         raise ValueError('flagella_step: a whole, unbanded plane')
     ld = location.shape[1]
     if motil.shape != (native.VK_MOTIL_ROWS, ld) or not (motil.is_contiguous() and location.is_contiguous()):

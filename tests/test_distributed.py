@@ -180,6 +180,14 @@ class _FakeColony:
     def agent_array_names(self):
         return ['params', 'counts', 'status', 'location', 'ordinal']
 
+    # the real capacity hook (install_agents calls it when ld grows), and what it reads
+    motility = mechanics = response = env_fields = _flag_expression = None
+    _layout = 0
+
+    def _capacity_scratch(self):
+        from lens_amd.colony import Colony
+        Colony._capacity_scratch(self)
+
 
 def _router_worker(rank, world, port, seed, q):
     from lens_amd.distributed import AgentRouter
