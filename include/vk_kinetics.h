@@ -36,7 +36,8 @@
  *       replaces get_bin_site (vivarium/library/lattice_utils.py:18-40).
  *   vk_cell_step / vk_divide_*, vk_kremling_step, vk_expression_step,
  *   vk_motility_step, vk_flagella_step, vk_contact_step, vk_contact_step_channels, vk_population_plan,
- *   vk_flagella_counts, vk_divide_flagella
+ *   vk_flagella_counts, vk_divide_flagella, vk_ssa_step, vk_ssa_propensities, vk_divide_counts,
+ *   vk_ssa_flagella_target
  *       are introduced by the comment blocks above their declarations.
  *
  * Conventions
@@ -735,6 +736,104 @@ int vk_divide_flagella(int64_t n_out, int64_t n_keep, int64_t n_src, const int32
                        const uint64_t *path_src, int32_t *flag_int_dst, int64_t ld_dst,
                        int64_t *key_dst, int32_t mode, uint64_t seed, uint64_t step, int64_t key_base,
                        vk_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Stochastic mass-action kinetics: the Gillespie direct method per agent
+ *
+ *   vk_ssa_step
+ *       stands where the reference calls arrow.StochasticSystem.evolve (Complexation,
+ *       vivarium/processes/complexation.py:74,120; the flagella complexes of
+ *       data/chromosomes/flagella_chromosome.py:371-453).  NOT bit-compatible with arrow:
+ *       the algorithm is the direct method in this library's own arithmetic and its own
+ *       Philox draws, stated below and restated in NumPy by tests/ssa_ref.py.
+ *   vk_ssa_propensities
+ *       the propensities alone, as vk_ssa_step evaluates them.
+ *   vk_divide_counts
+ *       the `_divide` branch of Store.apply_update for int counts with divide_split
+ *       (core/registry.py:205-227), one coin per (mother, species).
+ *   vk_ssa_flagella_target
+ *       the twin of vk_flagella_counts for an int source: FlagellaActivity reads the
+ *       'flagella' complex as internal_counts.flagella (chemotaxis_flagella.py:176-291).
+ * ------------------------------------------------------------------------- */
+
+#define VK_SSA_MAX_SPECIES 64
+#define VK_SSA_MAX_REACTIONS 32
+#define VK_SSA_MAX_ORDER 255
+
+/* Mixed into the seed of vk_ssa_step's draws and of vk_divide_counts' coins (seed ^ this). */
+#define VK_SSA_DOMAIN 0x7373615f73746570ULL
+#define VK_SSA_DIVIDE_DOMAIN 0x7373615f64697669ULL
+
+enum vk_ssa_status {            /* bits OR-ed into the caller's status[] by vk_ssa_step (never cleared) */
+    VK_SSA_MAX_EVENTS = 1,      /* the agent fired max_events events and was stopped there         */
+    VK_SSA_NONFINITE = 2,       /* the summed propensity was inf or NaN: stopped before the event  */
+    VK_SSA_OVERFLOW = 4,        /* an event would take a count past INT32_MAX: not fired, stopped  */
+    VK_SSA_BAD_KEY = 8          /* the agent's key lies outside [0, 2^31): not stepped             */
+};
+
+/* A network of n_species <= 64 species and n_reactions <= 32 reactions.  Every pointer is a
+ * DEVICE array the caller owns (the struct itself is read on the host at the call):
+ *   react_*   CSR of the reactants: reaction r consumes react_order[j] >= 1 (<= max_order)
+ *             molecules of species react_species[j] for j in [react_ptr[r], react_ptr[r+1]),
+ *             species ascending;
+ *   stoich_*  CSR of the whole stoichiometry: an event of r adds stoich_delta[j] to species
+ *             stoich_species[j];
+ *   rates     [n_reactions]; inv [n_inv]: inv[i] = 1.0 / (i + 1) in FP64, n_inv >= max_order. */
+typedef struct {
+    int32_t n_species, n_reactions, max_order, n_inv;
+    const int32_t *react_ptr, *react_species, *react_order;
+    const int32_t *stoich_ptr, *stoich_species, *stoich_delta;
+    const double *rates, *inv;
+} vk_ssa_net;
+
+/* One step of `duration` for agents [0, n) of counts [n_species][ld] (int32), one agent per
+ * lane, each on her own clock t = 0:
+ *   a_r    = rates[r] * prod C(x_s, k) over r's reactants in CSR order (no reactants: rates[r]);
+ *            C(n, k) = 0 if n < k, else c = 1.0; for i < k: c = c * (double)(n - i); c = c * inv[i]
+ *            (two FP64 multiplies per factor, no divide, no fused multiply-add);
+ *   total  = a_0 + a_1 + ... in reaction order, cum_r the running sums;
+ *   total == 0: the agent is done, no draw is consumed; total not finite: VK_SSA_NONFINITE, done;
+ *   draw e = 0, 1, ... of the step: one Philox4x32-10 block, key (seed ^ VK_SSA_DOMAIN), counter
+ *            (step, (int32) keys[a], e, 0); u1 from words 0 and 1, u2 from words 2 and 3 (the
+ *            (w >> 5, w >> 6) construction of the other kernels);
+ *   tau    = -log(1.0 - u1) / total; t + tau > duration: done, the event is discarded and
+ *            nothing carries into the next step; else t = t + tau;
+ *   fire   the first reaction q with cum_q > u2 * total (x += stoichiometry of q, one more
+ *            event), unless a count would pass INT32_MAX: VK_SSA_OVERFLOW, not fired, done;
+ *   the agent stops with VK_SSA_MAX_EVENTS once she has fired max_events (>= 1) events.
+ * step_counter: one device int64, the `step` word of this launch; the launch sequence then
+ * advances it by one (also for n = 0), so a captured graph replays successive steps.
+ * events_out [ld]: the events each agent fired.  status [ld]: vk_ssa_status bits are OR-ed in.
+ * An agent that fired nothing has no count written.  Draws depend on (seed, step, key, e)
+ * alone.  No atomics, no host synchronisation, no wait between workgroups.  */
+int vk_ssa_step(const vk_ssa_net *net, int64_t n_agents, int64_t ld, double duration, int32_t *counts,
+                const int64_t *keys, uint64_t seed, int64_t *step_counter, int32_t max_events,
+                int32_t *events_out, int32_t *status, vk_stream_t stream);
+
+/* out[r * ld + a] = a_r of agent a < n exactly as vk_ssa_step evaluates it from counts
+ * [n_species][ld] (the same device function).                                      */
+int vk_ssa_propensities(const vk_ssa_net *net, int64_t n_agents, int64_t ld, const int32_t *counts,
+                        double *out, vk_stream_t stream);
+
+/* divide_split on n_species rows of int32 counts over a plan of vk_divide_plan or
+ * vk_population_plan (slots [0, n_keep) are the survivors, the daughters follow; n_src agents
+ * in the source arrays).  Per slot j with a = src_index[j]:
+ *   survivor    her counts and key_src[a], copied;
+ *   daughter k  key_base + (j - n_keep) (the caller advances key_base by n_out - n_keep; the
+ *               last key must not pass 2^31 - 1); of each species s: half = x / 2 (toward zero),
+ *               and the odd one (x - 2 half) to daughter 0 when u < 0.5, else to daughter 1, with
+ *               u = Philox(key (seed ^ VK_SSA_DIVIDE_DOMAIN); counter (step, (int32) key_src[a],
+ *               s, 0)): one coin per (mother, species), the same for both daughters.       */
+int vk_divide_counts(int64_t n_out, int64_t n_keep, int64_t n_src, const int32_t *src_index,
+                     const int32_t *kind, const int32_t *counts_src, int64_t ld_src,
+                     const int64_t *key_src, int32_t *counts_dst, int64_t ld_dst, int64_t *key_dst,
+                     int32_t n_species, uint64_t seed, uint64_t step, int64_t key_base,
+                     vk_stream_t stream);
+
+/* target[a] = clamp(counts_row[a], 0, 32) for a < n.  flags: one device int32, set to 1 (never
+ * cleared) when a count was negative or above 32: the motor's mask holds 32 flagella.  */
+int vk_ssa_flagella_target(int64_t n_agents, const int32_t *counts_row, int32_t *target,
+                           int32_t *flags, vk_stream_t stream);
 
 /* Occupancy on the device: order[k] = the agent column with the k-th smallest
  * (bin_lin[a], key[a]) (key NULL: the column index; keys distinct, < 2^32),

@@ -57,6 +57,13 @@ growth and expression results are discarded while its membrane keeps leaking.
 The exchange then adds each agent's int64 kinetic counts and its float membrane
 counts to the field, agent after agent.
 
+With a :class:`~lens_amd.stochastic.StochasticModel` (``stochastic=``) every agent also
+carries the int counts of a mass-action network (``ssa``) and a key of her own for its
+draws (``ssa_key``); at the end of the step, where the expression step sits and before
+growth and division, the network advances by the Gillespie direct method (vk_ssa_step),
+and division splits the counts with the reference's ``divide_split`` (vk_divide_counts).
+``FlagellaModel(0, complexes='flagella')`` then takes the flagella count from that species.
+
 With a :class:`~lens_amd.cells.CellModel` the step continues like the
 reference's deriver pass: the growth process (from the step-start state),
 then TreeMass / DeriveGlobals (``mmol_to_counts`` for the next step's
@@ -83,6 +90,7 @@ from lens_amd.motility import (DeviceOccupancy, DIVISION_MODES, MotilityModel, R
                                FLAGI_ROW_NAMES, check_flagella_counts, flagella_step, motility_step)
 from lens_amd.rate_law_compiler import compile_rate_laws, RateLawTable
 from lens_amd.response import CellResponse, ResponseBuffers, ResponseEngine
+from lens_amd.stochastic import StochasticEngine, StochasticModel, describe_status, divide_counts, flagella_target
 
 
 def mmol_to_counts_from_mass(mass_fg, density_g_per_L=1100.0, avogadro=N_A_LEGACY):
@@ -115,9 +123,15 @@ AGENT_ARRAYS = (
     ('ordinal', 'given'),                # the router's global order, computed by a collective
     ('env_fields', _SET),                # NonSpatialEnvironment: each agent's own 1x1 field
 )
+# The per-agent arrays of Colony(stochastic=...), two more rows of the same table, reported
+# after the ones above: the int counts of the stochastic network, split by divide_split with
+# a coin per (mother, species), and the key each agent draws by; daughters get fresh keys
+# (vk_divide_counts)
+STOCHASTIC_ARRAYS = (('ssa', 'counts'), ('ssa_key', 'counts'))
+_ALL_AGENT_ARRAYS = AGENT_ARRAYS + STOCHASTIC_ARRAYS
 # Tensors sized by the capacity that are not per-agent state: Colony._capacity_scratch
 # allocates them (the first row) or drops them for their users to allocate again (the second)
-CAPACITY_SCRATCH = ('bin_lin', 'bin_ix', 'env_bins', 'outflow', '_flag_expr_update',
+CAPACITY_SCRATCH = ('bin_lin', 'bin_ix', 'env_bins', 'outflow', '_flag_expr_update', 'ssa_events', '_ssa_status',
                     '_counts_alt', 'flux_steps', 'counts_steps', 'nsteps_steps')
 
 
@@ -126,7 +140,8 @@ class Colony:
     location = ordinal = env_fields = None       # set with a lattice / by the router / nonspatial
     agent_order = None       # sort_by_bin: the reference index of the agent in each column
     attempts = None          # count_attempts
-    _flag_expression = _flag_flags = None        # FlagellaModel(expression=...)
+    _flag_expression = _flag_flags = None        # FlagellaModel(expression=...) / (complexes=...)
+    stochastic = _ssa = ssa = ssa_key = None     # Colony(stochastic=...)
     _x_stream = _p_stream = None                 # capture(overlap=True)
     _counts_alt = flux_steps = counts_steps = nsteps_steps = None    # capture(overlap=True), step_many
 
@@ -136,7 +151,8 @@ class Colony:
                  avogadro: float = N_A_LEGACY, exchange: str = 'sorted', mass_fg: float = 1339.0,
                  table: Optional[RateLawTable] = None, specialize: bool = False,
                  cells: Optional[CellModel] = None, agent_ids=None, motility: Optional[MotilityModel] = None,
-                 mechanics: Optional[ContactModel] = None, response: Optional[CellResponse] = None):
+                 mechanics: Optional[ContactModel] = None, response: Optional[CellResponse] = None,
+                 stochastic: Optional[StochasticModel] = None):
         if integrator not in ('euler', 'dopri5'):
             raise ValueError('integrator must be euler or dopri5')
         if exchange not in ('sorted', 'atomic'):
@@ -155,6 +171,23 @@ class Colony:
             if cells is not None and motility.division is None:
                 # the model must say how the motile state divides (MotilityModel(division=...))
                 raise ValueError('motility with cells (growth and division) is not supported')
+        complexes = motility.flagella.complexes if motility is not None and motility.flagella is not None else None
+        if complexes is not None and stochastic is None:
+            raise ValueError('FlagellaModel(complexes=%r) needs a colony with stochastic=StochasticModel(...)' % (
+                complexes,))
+        if stochastic is not None:
+            # checked before anything is built: the draws go by a key per agent that is not
+            # global across ranks, and a frozen agent would need its counts saved and restored
+            if not isinstance(stochastic, StochasticModel):
+                raise ValueError('stochastic must be a StochasticModel')
+            if isinstance(environment, Lattice) and not whole_plane(environment):
+                raise ValueError('stochastic needs a whole, unbanded plane (row bands are not supported: the draw '
+                                 'keys are not global across ranks)')
+            if response is not None:
+                raise ValueError('stochastic with response is not supported (a frozen agent would need its counts '
+                                 'saved and restored)')
+            if complexes is not None:
+                stochastic.index(complexes)      # ValueError: the network has no such species
         if mechanics is not None:
             # checked before anything is built, like motility: the contact launch moves and
             # re-bins the agents on the device, on one whole plane
@@ -251,6 +284,14 @@ class Colony:
         self.cells = cells
         self.motility = motility
         self.mechanics = mechanics
+        self.stochastic = stochastic
+        if stochastic is not None:
+            # the network on the device, the int counts and the key each agent draws by for
+            # life (daughters get fresh ones); the engine's step word lives on the device
+            self._ssa = StochasticEngine(stochastic, dev)
+            self.ssa = torch.from_numpy(stochastic.initial_counts(self.n, ld)).to(dev).contiguous()
+            self.ssa_key = torch.arange(ld, dtype=torch.int64, device=dev)
+            self._ssa_key_base = self.n
         if response is not None:
             self.dead = z(ld, dtype=torch.int32)
             self.frozen = z(ld, dtype=torch.int32)
@@ -301,6 +342,10 @@ class Colony:
                     self._flag_expression = ExpressionEngine(fm.expression_table, dev)
                     self._flag_flags = z(1, dtype=torch.int32)
                     self._flagella_counts()
+                if complexes is not None:
+                    # the flagella count follows the stochastic network's complex; once at t = 0
+                    self._flag_flags = z(1, dtype=torch.int32)
+                    self._ssa_flagella()
             if mechanics is not None and cells is None:
                 self.mech_angle = torch.from_numpy(mechanics.initial_angles(self.n, ld)).to(dev).contiguous()
         elif environment == 'nonspatial':
@@ -357,6 +402,10 @@ class Colony:
         if self._flag_expression is not None:
             self._flag_expr_update = torch.zeros((len(self._flag_expression.table.outputs), ld),
                                                  dtype=torch.float64, device=dev)
+        if getattr(self, 'stochastic', None) is not None:       # objects that only borrow this hook lack it
+            # the events each agent fired in the last step; the status bits are sticky and
+            # checked before the capacity changes (_regather), so nothing is lost here
+            self.ssa_events, self._ssa_status = i32(), i32()
         # sized by ld too, allocated by their users (capture(overlap=True), step_many)
         self._counts_alt = self.flux_steps = self.counts_steps = self.nsteps_steps = None
         self._layout += 1
@@ -430,6 +479,9 @@ class Colony:
         if self.motility.flagella.expression is not None:
             raise ValueError('set_flagella: the count is derived from the expressed protein every step '
                              '(FlagellaModel(expression=...)) and would be overwritten')
+        if self.motility.flagella.complexes is not None:
+            raise ValueError('set_flagella: the count follows the stochastic network\'s complex every step '
+                             '(FlagellaModel(complexes=...)) and would be overwritten')
         row = self.flag_int[native.VK_FLAGI_TARGET, :self.n]
         if torch.is_tensor(counts) and counts.device.type == self.device.type and self.device.type != 'cpu':
             if counts.dtype != torch.int32 or counts.dim() != 1 or counts.shape[0] < self.n:
@@ -447,7 +499,7 @@ class Colony:
     def agent_array_names(self):
         """Every per-agent array this colony has (agent = column), as attribute names in
         the order of AGENT_ARRAYS: what division gathers and the router migrates."""
-        return [name for name, _ in AGENT_ARRAYS if torch.is_tensor(getattr(self, name, None))]
+        return [name for name, _ in _ALL_AGENT_ARRAYS if torch.is_tensor(getattr(self, name, None))]
 
     def refresh_bins(self):
         """Recompute bin sites and the agent-ordered bin occupancy (after moves).
@@ -610,6 +662,8 @@ class Colony:
         the last step's."""
         if self.response is not None:
             raise ValueError('step_many: a colony with a response steps with step()')
+        if self.stochastic is not None:
+            raise ValueError('step_many: a colony with stochastic kinetics steps with step()')
         if self.environment != 'held' or self.cells is not None or self.integrator != 'dopri5':
             raise ValueError('step_many: held externals, no division, DP45 (agents must not couple between steps)')
         k = int(steps)
@@ -740,6 +794,8 @@ class Colony:
             raise ValueError('a colony with mechanics steps with step(): the contacts run on the step clock')
         if self.response is not None:
             raise ValueError('a colony with a response steps with step(): its processes share the step clock')
+        if self.stochastic is not None:
+            raise ValueError('a colony with stochastic kinetics steps with step(): its step runs on the step clock')
         procs = [('diffusion', float(diffusion_dt)), ('kinetics', float(kinetics_dt))]   # store order
         front = {name: 0.0 for name, _ in procs}      # every update() call starts its fronts at 0
         pending = {}
@@ -1149,6 +1205,28 @@ class Colony:
             raise FloatingPointError('a derived flagella count left 0..32 (concentration * mmol_to_counts was '
                                      'negative, not a number or 33 and more): the motor holds 32 flagella')
 
+    def _ssa_complex(self):
+        """The species whose count is the flagella count (FlagellaModel(complexes=...)), or None."""
+        m = self.motility
+        return m.flagella.complexes if m is not None and m.flagella is not None else None
+
+    def _ssa_flagella(self):
+        """target := the agent's count of the flagella complex, 0..32 (vk_ssa_flagella_target)."""
+        row = self.stochastic.index(self._ssa_complex())
+        flagella_target(self.n, self.ssa[row], self.flag_int[native.VK_FLAGI_TARGET], self._flag_flags)
+
+    def _ssa_check(self):
+        """Raises if a stochastic step ever set a status bit (one host read: called where the
+        host reads from the device anyway, and by check_status)."""
+        if self._ssa is None:
+            return
+        st = self._ssa_status[:self.n]
+        bad = torch.nonzero(st).flatten()
+        if bad.numel():
+            a = int(bad[0])
+            raise FloatingPointError('agent %d: stochastic step status %d (%s)' % (
+                a, int(st[a]), describe_status(int(st[a]))))
+
     def _finish_step(self, dt):
         if self._flag_expression is not None:
             # the expression process from the step-start state (ode_expression.py:265-303), then
@@ -1156,6 +1234,14 @@ class Colony:
             # the mmol_to_counts the previous step left; both before vk_cell_step touches m2c
             self._flag_expression.step(dt, self.flag_expr, self.n, update=self._flag_expr_update, accumulate=True)
             self._flagella_counts()
+        if self._ssa is not None:
+            # the stochastic network over the step, every agent on her own clock and by her own
+            # key; then the flagella count the NEXT step's motor reads (the reference's
+            # FlagellaActivity sees the counts the previous step left).  Before division, which
+            # splits the post-step counts
+            self._ssa.step(dt, self.ssa, self.ssa_key, self.n, events=self.ssa_events, status=self._ssa_status)
+            if self._ssa_complex() is not None:
+                self._ssa_flagella()
         if self.cells is not None:
             self.grow_and_divide(dt)
         elif self._channels():
@@ -1280,6 +1366,9 @@ class Colony:
         if self.motility is not None and self._key_base + 2 * (n_out - self.n) - 1 > 2 ** 31 - 1:
             # before any array is gathered into the new layout
             raise OverflowError('a motility key would pass 2**31 - 1 (the kernels put it into a 32-bit counter word)')
+        if self.stochastic is not None and self._ssa_key_base + n_out - 1 > 2 ** 31 - 1:
+            # at most n_out daughters
+            raise OverflowError('a stochastic key would pass 2**31 - 1 (the kernel puts it into a 32-bit counter word)')
         ld = self.ld if n_out <= self.ld else max(n_out, int(self.ld * 1.25) + 64)
         self._regather(n_out, src, kind, ld, ordinal=ordinal)
         if int(self._overflow.item()):
@@ -1294,6 +1383,7 @@ class Colony:
         the new ones are installed together, then the scratch follows the capacity and the
         bins and occupancies are rebuilt."""
         dev, st, n, ld_src = self.device, native.stream_handle(), self.n, self.ld
+        self._ssa_check()                    # the status bits go by column: read before the columns move
         alloc = torch.empty if declared else torch.zeros
         plan = (n_out, native.ptr(src), native.ptr(kind))
         new = {}
@@ -1310,7 +1400,7 @@ class Colony:
             return out
 
         old = {name: getattr(self, name) for name in self.agent_array_names()}
-        for name, divider in AGENT_ARRAYS:
+        for name, divider in _ALL_AGENT_ARRAYS:
             if name not in old:
                 continue
             if not declared:
@@ -1351,12 +1441,23 @@ class Colony:
                     ld, native.ptr(new['motile_key']), DIVISION_MODES[m.division], m.seed & (2 ** 64 - 1),
                     self.step_index & (2 ** 64 - 1), self._key_base, st), 'vk_divide_flagella')
                 self._key_base += n_daughters
+            if 'ssa' in old:
+                # divide_split on every species, a coin per (mother, species) keyed by the
+                # mother's key.  The plan may hold removed agents (vk_population_plan), so the
+                # daughters are counted: one more host read where the host reads anyway
+                n_daughters = int((kind[:n_out] >= 0).sum())
+                new['ssa'], new['ssa_key'] = empty(old['ssa']), empty(old['ssa_key'])
+                divide_counts(n_out, n_out - n_daughters, n, src, kind, old['ssa'], old['ssa_key'], new['ssa'],
+                              new['ssa_key'], self.stochastic.seed, self.step_index, self._ssa_key_base)
+                self._ssa_key_base += n_daughters
         for name, t in new.items():
             setattr(self, name, t)
         self.n = n_out
         if ld != self.ld:
             self.ld = ld
             self._capacity_scratch()
+        if declared and 'ssa' in old and self._ssa_complex() is not None:
+            self._ssa_flagella()         # the daughters' motors read their own share of the complex
         if self.lattice is not None:
             self.refresh_bins()          # bins, host and device occupancy, the _layout bump
         else:
@@ -1379,6 +1480,7 @@ class Colony:
             self._mech.check()
         if self.motility is not None:
             self._flagella_check()
+        self._ssa_check()
 
     # -- views ----------------------------------------------------------------------
     def species(self, port, name):
@@ -1427,4 +1529,9 @@ class Colony:
                                 'location': self.location[:, :self.n].cpu().numpy().copy()}
         if self.response is not None:
             out.setdefault('global', {})['dead'] = self.dead[:self.n].cpu().numpy().copy()
+        if self.stochastic is not None:
+            x = self.ssa[:, :self.n].cpu().numpy()
+            out['stochastic'] = {name: x[row].copy() for row, name in enumerate(self.stochastic.species)}
+            out['ssa_key'] = self.ssa_key[:self.n].cpu().numpy().copy()
+            out['ssa_events'] = self.ssa_events[:self.n].cpu().numpy().copy()
         return out

@@ -35,3 +35,24 @@ __device__ __forceinline__ double philox_uniform(uint64_t seed, uint64_t step, i
     const double a = (double)(c[0] >> 5), b = (double)(c[1] >> 6);
     return (a * 67108864.0 + b) / 9007199254740992.0;
 }
+
+// two uniform doubles of ONE block: u1 from words 0 and 1 (what philox_uniform returns for the
+// same arguments), u2 from words 2 and 3 by the same construction (vk_ssa.hip: the waiting time
+// and the reaction of one Gillespie event)
+__device__ __forceinline__ void philox_uniform_pair(uint64_t seed, uint64_t step, int32_t root, int32_t depth,
+                                                    uint64_t path, double &u1, double &u2) {
+    uint32_t c[4] = {(uint32_t)step, (uint32_t)root, (uint32_t)path, (uint32_t)(path >> 32)};
+    uint32_t k[2] = {(uint32_t)seed + (uint32_t)depth, (uint32_t)(seed >> 32)};
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        if (r) {
+            k[0] += 0x9E3779B9u;
+            k[1] += 0xBB67AE85u;
+        }
+        philox_round(c, k);
+    }
+    const double a = (double)(c[0] >> 5), b = (double)(c[1] >> 6);
+    const double d = (double)(c[2] >> 5), e = (double)(c[3] >> 6);
+    u1 = (a * 67108864.0 + b) / 9007199254740992.0;
+    u2 = (d * 67108864.0 + e) / 9007199254740992.0;
+}

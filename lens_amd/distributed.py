@@ -154,6 +154,9 @@ class AgentRouter:
         if col.mechanics is not None:
             raise ValueError('AgentRouter: a colony with mechanics (Colony(mechanics=...)) takes no router: its '
                              'agents move and re-bin on one device, on a whole plane')
+        if getattr(col, 'stochastic', None) is not None:
+            raise ValueError('AgentRouter: a colony with stochastic kinetics (Colony(stochastic=...)) takes no '
+                             'router: its draw keys are not global across ranks')
         lat = col.lattice
         bands = row_bands(lat.n_bins[0], world)
         if (lat.row_lo_global, lat.row_hi_global) != bands[rank]:

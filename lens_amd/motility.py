@@ -106,10 +106,23 @@ class FlagellaModel:
     ``n_flagella`` then is only the number of flagella the agents start with (the
     reference's agent: 0).  The configuration's states all live under ``'internal'``;
     regulators on other ports and a transcription leak (host draws that cannot be
-    replayed) are refused."""
+    replayed) are refused.
 
-    def __init__(self, n_flagella=5, expression=None, count_of='flagella', **parameters):
+    ``complexes`` (a species id, e.g. ``'flagella'``) takes the count from the colony's
+    stochastic network instead (``Colony(stochastic=StochasticModel(...))``), as in the
+    reference's ChemotaxisExpressionFlagella (chemotaxis_flagella.py:176-291), where
+    ``Complexation`` assembles the ``'flagella'`` complex: after every stochastic step, and
+    once at t = 0, the count is the agent's int count of that species, 0..32
+    (vk_ssa_flagella_target).  It does not combine with ``expression``."""
+
+    def __init__(self, n_flagella=5, expression=None, count_of='flagella', complexes=None, **parameters):
         self.expression, self.count_of, self.expression_table = None, count_of, None
+        if complexes is not None and expression is not None:
+            raise ValueError('flagella: the count follows either an expressed protein (expression=) or a complex '
+                             'of the stochastic network (complexes=), not both')
+        if complexes is not None and not isinstance(complexes, str):
+            raise ValueError('flagella: complexes must be the id of a species of the colony\'s stochastic network')
+        self.complexes = complexes
         if expression is not None:
             self._compile_expression(expression, count_of)
         unknown = set(parameters) - set(FLAGELLA_DEFAULTS)

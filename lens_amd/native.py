@@ -36,6 +36,7 @@ EXPORTS = (
     'vk_response_begin', 'vk_response_end', 'vk_response_cells', 'vk_exchange_ordered_mixed',
     'vk_exchange_atomic_f64', 'vk_population_scratch_bytes', 'vk_population_plan', 'vk_contact_step_channels',
     'vk_flagella_step', 'vk_flagella_counts', 'vk_divide_flagella',
+    'vk_ssa_step', 'vk_ssa_propensities', 'vk_divide_counts', 'vk_ssa_flagella_target',
 )
 
 VK_CELL_MASS, VK_CELL_VOLUME, VK_CELL_LENGTH, VK_CELL_SURFACE_AREA, VK_CELL_PROTEIN, VK_CELL_ANGLE = range(6)
@@ -49,6 +50,10 @@ VK_FLAGI_TARGET, VK_FLAGI_HAVE, VK_FLAGI_MASK = range(3)
 VK_FLAGI_ROWS = 3
 VK_FLAGELLA_MERGED, VK_FLAGELLA_SPLIT_DICT = 0, 1
 VK_DIVIDE_FLAGELLA_DOMAIN = 0x666c6167656c6c61     # mixed into the seed of vk_divide_flagella's draw
+VK_SSA_MAX_SPECIES, VK_SSA_MAX_REACTIONS, VK_SSA_MAX_ORDER = 64, 32, 255
+VK_SSA_DOMAIN = 0x7373615f73746570                 # mixed into the seed of vk_ssa_step's draws
+VK_SSA_DIVIDE_DOMAIN = 0x7373615f64697669          # and of vk_divide_counts' coins
+VK_SSA_MAX_EVENTS, VK_SSA_NONFINITE, VK_SSA_OVERFLOW, VK_SSA_BAD_KEY = 1, 2, 4, 8
 VK_GROWTH_PROTEIN, VK_GROWTH_MASS = 0, 1
 VK_RNG_STREAM, VK_RNG_PHILOX = 0, 1
 VK_DIVIDE_SET, VK_DIVIDE_SPLIT, VK_DIVIDE_ZERO = 0, 1, 2
@@ -130,6 +135,12 @@ class VkResponseTable(ctypes.Structure):
                            'save_row', 'expr_row')] + [('avogadro', ctypes.c_double), ('volume_fl', ctypes.c_double)]
 
 
+class VkSsaNet(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('n_species', 'n_reactions', 'max_order', 'n_inv')] + [
+        (n, _vp) for n in ('react_ptr', 'react_species', 'react_order', 'stoich_ptr', 'stoich_species',
+                           'stoich_delta', 'rates', 'inv')]
+
+
 _SIGS = {
     'vk_abi_version': ([], ctypes.c_int),
     'vk_last_error': ([], ctypes.c_char_p),
@@ -181,6 +192,12 @@ _SIGS = {
     'vk_flagella_counts': ([_i64, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     'vk_divide_flagella': ([_i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32,
                             ctypes.c_uint64, ctypes.c_uint64, _i64, _vp], ctypes.c_int),
+    'vk_ssa_step': ([ctypes.POINTER(VkSsaNet), _i64, _i64, _f64, _vp, _vp, ctypes.c_uint64, _vp, _i32, _vp, _vp, _vp],
+                    ctypes.c_int),
+    'vk_ssa_propensities': ([ctypes.POINTER(VkSsaNet), _i64, _i64, _vp, _vp, _vp], ctypes.c_int),
+    'vk_divide_counts': ([_i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i32, ctypes.c_uint64,
+                          ctypes.c_uint64, _i64, _vp], ctypes.c_int),
+    'vk_ssa_flagella_target': ([_i64, _vp, _vp, _vp, _vp], ctypes.c_int),
     'vk_occupancy_scratch_bytes': ([_i64], ctypes.c_int64),
     'vk_occupancy_sort': ([_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp], ctypes.c_int),
     'vk_exchange_ordered': ([_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _f64, _vp], ctypes.c_int),

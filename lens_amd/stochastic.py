@@ -1,0 +1,240 @@
+"""Stochastic mass-action kinetics per agent: batched Gillespie steps.
+
+The reference integrates ``Complexation`` (vivarium/processes/complexation.py:74,120)
+with the Gillespie direct method of ``arrow.StochasticSystem``.  Here a network is
+packed once into a few small device arrays (:class:`StochasticModel`,
+:class:`StochasticEngine`) and every agent of a colony advances by one launch per
+timestep (vk_ssa_step): one agent per lane, her counts a column of an int32
+``[species][ld]`` array, her draws keyed by a key of her own.
+
+This is NOT arrow's arithmetic nor its random stream.  The step is stated above
+``vk_ssa_step`` in include/vk_kinetics.h and restated in NumPy by tests/ssa_ref.py;
+DESIGN.md §17 says what is and what is not the reference.
+
+``Colony(..., stochastic=StochasticModel(...))`` keeps the counts (``ssa``) and the
+keys (``ssa_key``) per agent, steps them at the end of every timestep and divides
+them with the reference's ``divide_split`` (vk_divide_counts).
+"""
+
+from __future__ import annotations
+
+import ctypes
+from typing import Dict, Optional, Sequence
+
+import numpy as np
+
+from lens_amd import native
+
+MAX_SPECIES, MAX_REACTIONS, MAX_ORDER = native.VK_SSA_MAX_SPECIES, native.VK_SSA_MAX_REACTIONS, native.VK_SSA_MAX_ORDER
+STATUS_NAMES = ((native.VK_SSA_MAX_EVENTS, 'max_events reached'), (native.VK_SSA_NONFINITE, 'propensity not finite'),
+                (native.VK_SSA_OVERFLOW, 'a count would pass 2**31 - 1'), (native.VK_SSA_BAD_KEY, 'key outside [0, 2**31)'))
+
+
+def describe_status(bits: int) -> str:
+    return ', '.join(text for bit, text in STATUS_NAMES if bits & bit) or 'ok'
+
+
+def _whole(value, what):
+    """An int from an int or a float with an integral value (the reference writes -4.0)."""
+    if isinstance(value, (bool, np.bool_)):
+        raise ValueError('%s: %r is not a whole number' % (what, value))
+    try:
+        f = float(value)
+    except (TypeError, ValueError):
+        raise ValueError('%s: %r is not a whole number' % (what, value))
+    if f != f or f in (float('inf'), float('-inf')) or f != int(f):
+        raise ValueError('%s: %r is not a whole number' % (what, value))
+    return int(f)
+
+
+class StochasticModel:
+    """A mass-action network in the reference's shape.
+
+    ``species``: the ids, in row order.  ``stoichiometry``: ``{reaction: {species: int}}``;
+    a negative entry makes the species a reactant of that order.  ``rates``:
+    ``{reaction: rate}`` (or a sequence in the stoichiometry's order).  ``initial``:
+    ``{species: count}`` (default 0) every agent starts with.  The reactions keep the
+    stoichiometry's order; within a reaction the species are sorted by row."""
+
+    def __init__(self, species: Sequence[str], stoichiometry: Dict[str, Dict[str, int]], rates,
+                 initial: Optional[Dict[str, int]] = None, seed: int = 0, max_events: int = 100000):
+        self.species = [str(s) for s in species]
+        if len(set(self.species)) != len(self.species):
+            raise ValueError('stochastic: species ids must be distinct')
+        S = len(self.species)
+        if not 1 <= S <= MAX_SPECIES:
+            raise ValueError('stochastic: 1..%d species (got %d)' % (MAX_SPECIES, S))
+        if not isinstance(stoichiometry, dict):
+            raise ValueError('stochastic: stoichiometry must be {reaction: {species: int}}')
+        self.reactions = list(stoichiometry.keys())
+        R = len(self.reactions)
+        if not 1 <= R <= MAX_REACTIONS:
+            raise ValueError('stochastic: 1..%d reactions (got %d)' % (MAX_REACTIONS, R))
+        row = {s: i for i, s in enumerate(self.species)}
+        self.matrix = np.zeros((R, S), dtype=np.int64)
+        for r, rid in enumerate(self.reactions):
+            for sp, value in stoichiometry[rid].items():
+                if sp not in row:
+                    raise ValueError('stochastic: reaction %r names the unknown species %r' % (rid, sp))
+                v = _whole(value, 'stochastic: stoichiometry of %r in %r' % (sp, rid))
+                if v < -MAX_ORDER:
+                    raise ValueError('stochastic: reactant order %d of %r in %r exceeds %d' % (-v, sp, rid, MAX_ORDER))
+                if v > 2 ** 31 - 1:
+                    raise ValueError('stochastic: stoichiometry of %r in %r does not fit int32' % (sp, rid))
+                self.matrix[r, row[sp]] = v
+        if isinstance(rates, dict):
+            unknown = set(rates) - set(self.reactions)
+            if unknown:
+                raise ValueError('stochastic: rates for unknown reactions %s' % sorted(map(str, unknown)))
+            missing = [rid for rid in self.reactions if rid not in rates]
+            if missing:
+                raise ValueError('stochastic: no rate for %s' % missing)
+            rates = [rates[rid] for rid in self.reactions]
+        self.rates = np.asarray(rates, dtype=np.float64).reshape(-1)
+        if self.rates.shape[0] != R or not np.all(np.isfinite(self.rates)) or np.any(self.rates < 0):
+            raise ValueError('stochastic: one finite rate >= 0 per reaction')
+        self.initial = np.zeros(S, dtype=np.int32)
+        for sp, value in (initial or {}).items():
+            if sp not in row:
+                raise ValueError('stochastic: initial names the unknown species %r' % (sp,))
+            v = _whole(value, 'stochastic: initial count of %r' % (sp,))
+            if not 0 <= v <= 2 ** 31 - 1:
+                raise ValueError('stochastic: initial count of %r must lie in 0..2**31 - 1' % (sp,))
+            self.initial[row[sp]] = v
+        self.seed = int(seed)
+        self.max_events = _whole(max_events, 'stochastic: max_events')
+        if not 1 <= self.max_events <= 2 ** 31 - 1:
+            raise ValueError('stochastic: max_events must lie in 1..2**31 - 1')
+        # the packed arrays (vk_ssa_net): reactant CSR and full-stoichiometry CSR, species ascending
+        rp, rs, ro, sp_, ss, sd = [0], [], [], [0], [], []
+        for r in range(R):
+            for s in range(S):
+                v = int(self.matrix[r, s])
+                if v < 0:
+                    rs.append(s)
+                    ro.append(-v)
+                if v != 0:
+                    ss.append(s)
+                    sd.append(v)
+            rp.append(len(rs))
+            sp_.append(len(ss))
+        i32 = lambda a: np.asarray(a, dtype=np.int32)
+        self.react_ptr, self.react_species, self.react_order = i32(rp), i32(rs), i32(ro)
+        self.stoich_ptr, self.stoich_species, self.stoich_delta = i32(sp_), i32(ss), i32(sd)
+        self.max_order = int(max(ro)) if ro else 0
+        # inv[i] = 1.0 / (i + 1) in FP64: the choose() of the kernel multiplies by it
+        self.inv = 1.0 / np.arange(1, MAX_ORDER + 1, dtype=np.float64)
+
+    @property
+    def n_species(self):
+        return len(self.species)
+
+    @property
+    def n_reactions(self):
+        return len(self.reactions)
+
+    def index(self, species: str) -> int:
+        if species not in self.species:
+            raise ValueError('stochastic: no species %r (species: %s)' % (species, self.species))
+        return self.species.index(species)
+
+    def initial_counts(self, n: int, ld: int) -> np.ndarray:
+        out = np.zeros((self.n_species, ld), dtype=np.int32)
+        out[:, :n] = self.initial[:, None]
+        return out
+
+
+_PACKED = ('react_ptr', 'react_species', 'react_order', 'stoich_ptr', 'stoich_species', 'stoich_delta', 'rates', 'inv')
+
+
+class StochasticEngine:
+    """A :class:`StochasticModel` resident on one GPU.  The engine holds the packed network
+    as torch tensors; the library owns none of it."""
+
+    def __init__(self, model: StochasticModel, device=None):
+        import torch
+        native.load()
+        if not isinstance(model, StochasticModel):
+            raise ValueError('StochasticEngine: a StochasticModel')
+        self.model = model
+        self.device = native.resolve_device(device)
+        self._dev = {}
+        for k in _PACKED:
+            a = np.ascontiguousarray(getattr(model, k))
+            if a.size == 0:
+                a = np.zeros(1, dtype=a.dtype)           # a network without reactants: no null pointers
+            self._dev[k] = torch.from_numpy(a).to(self.device)
+        # the step word of the next launch: on the device, advanced by each launch, so graphs replay it
+        self.step_counter = torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def net(self) -> native.VkSsaNet:
+        m, d = self.model, native.VkSsaNet()
+        d.n_species, d.n_reactions, d.max_order, d.n_inv = m.n_species, m.n_reactions, m.max_order, len(m.inv)
+        for k, v in self._dev.items():
+            setattr(d, k, v.data_ptr())
+        return d
+
+    def _check_counts(self, counts, n, what):
+        import torch
+        S = self.model.n_species
+        if (not torch.is_tensor(counts) or counts.dtype != torch.int32 or counts.dim() != 2 or counts.shape[0] != S or
+                not counts.is_contiguous()):
+            raise ValueError('%s: counts must be a contiguous int32 [%d, ld] device tensor' % (what, S))
+        ld = counts.shape[1]
+        n = ld if n is None else int(n)
+        if not 0 <= n <= ld:
+            raise ValueError('%s: 0 <= n <= ld' % what)
+        return n, ld
+
+    def step(self, duration, counts, keys, n=None, events=None, status=None, step_counter=None, max_events=None,
+             seed=None):
+        """One vk_ssa_step launch on the current stream for agents [0, n) of ``counts``
+        [S, ld] (int32) with ``keys`` [ld] (int64, each in [0, 2**31)).  ``step_counter`` (one
+        device int64, default the engine's own) is read and advanced.  Returns (events
+        [ld] int32, status [ld] int32: VK_SSA_* bits OR-ed in)."""
+        import torch
+        n, ld = self._check_counts(counts, n, 'StochasticEngine.step')
+        if not torch.is_tensor(keys) or keys.dtype != torch.int64 or keys.dim() != 1 or keys.shape[0] < n:
+            raise ValueError('StochasticEngine.step: keys must be an int64 device tensor over the agents')
+        if events is None:
+            events = torch.zeros(ld, dtype=torch.int32, device=self.device)
+        if status is None:
+            status = torch.zeros(ld, dtype=torch.int32, device=self.device)
+        counter = self.step_counter if step_counter is None else step_counter
+        m = self.model
+        d = self.net()
+        native.check(native._lib.vk_ssa_step(
+            ctypes.byref(d), n, ld, float(duration), native.ptr(counts), native.ptr(keys),
+            (m.seed if seed is None else int(seed)) & (2 ** 64 - 1), native.ptr(counter),
+            int(m.max_events if max_events is None else max_events), native.ptr(events), native.ptr(status),
+            native.stream_handle()), 'vk_ssa_step')
+        return events, status
+
+    def propensities(self, counts, n=None, out=None):
+        """a_r of every agent as the step evaluates it: float64 [R, ld]."""
+        import torch
+        n, ld = self._check_counts(counts, n, 'StochasticEngine.propensities')
+        if out is None:
+            out = torch.zeros((self.model.n_reactions, ld), dtype=torch.float64, device=self.device)
+        d = self.net()
+        native.check(native._lib.vk_ssa_propensities(
+            ctypes.byref(d), n, ld, native.ptr(counts), native.ptr(out), native.stream_handle()),
+            'vk_ssa_propensities')
+        return out
+
+
+def divide_counts(n_out, n_keep, n_src, src, kind, counts_src, key_src, counts_dst, key_dst, seed, step, key_base):
+    """vk_divide_counts on the current stream (see include/vk_kinetics.h)."""
+    native.check(native._lib.vk_divide_counts(
+        int(n_out), int(n_keep), int(n_src), native.ptr(src), native.ptr(kind), native.ptr(counts_src),
+        counts_src.shape[-1], native.ptr(key_src), native.ptr(counts_dst), counts_dst.shape[-1], native.ptr(key_dst),
+        counts_src.shape[0], int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), int(key_base),
+        native.stream_handle()), 'vk_divide_counts')
+
+
+def flagella_target(n, counts_row, target, flags):
+    """vk_ssa_flagella_target on the current stream: ``target[:n] = clamp(counts_row[:n], 0, 32)``;
+    ``counts_row`` / ``target``: int32 device rows (views), ``flags``: one device int32."""
+    native.check(native._lib.vk_ssa_flagella_target(
+        int(n), native.ptr(counts_row), native.ptr(target), native.ptr(flags), native.stream_handle()),
+        'vk_ssa_flagella_target')
