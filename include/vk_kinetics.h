@@ -284,6 +284,35 @@ int vk_diffuse_coupled(double *field, double *work0, double *work1, int32_t n_fi
                        const int32_t *count_row, const int64_t *counts, int64_t counts_ld,
                        double binvol_avogadro, vk_stream_t stream);
 
+/* The passes that vk_diffuse_part (part, interior_passes; VK_PART_ALL = vk_diffuse)
+ * would launch for this geometry under the current vk_set_stencil_* settings, in
+ * launch order; host only, launches nothing.  coupled != 0: vk_diffuse_coupled's
+ * whole-plane step instead (row_lo = lo_min = sub_begin = 0, row_hi = hi_max = rows,
+ * both edges, sub_count = n_sub, VK_PART_ALL), without or with agents.  Writes
+ * min(*n_passes, capacity) passes to `out` (nullable when capacity = 0) and the
+ * plan's length to *n_passes.  Returns VK_OK, VK_ERR_ARG for a geometry the call
+ * would refuse, or VK_ERR_LIMIT (*n_passes = 0) where it has no plan: a part of
+ * a block that does not split, a coupled step of fewer than two fused passes.
+ * A pass of k substeps reads rows [in_lo, in_hi) of buffer src and writes rows
+ * [lo, hi) of buffer dst, without [gap_lo, gap_hi) if gap_lo >= 0; f0: it is
+ * handed the step-start field as base; couple: bit 0 = it gathers first, bit 1 =
+ * it applies the exchange last; copy_back: the owned rows of work0 are copied to
+ * the field after it.  Not a reference interface: the launch list of the same
+ * reference call as vk_diffuse (diffusion_field.py:385-407).                 */
+enum { VK_BUF_FIELD = 0, VK_BUF_WORK0 = 1, VK_BUF_WORK1 = 2 };
+enum { VK_PASS_SINGLE = 0, VK_PASS_WL3, VK_PASS_WL6, VK_PASS_WL6NT, VK_PASS_PS, VK_PASS_PS10,
+       VK_PASS_PS10_ALIGNED, VK_PASS_PS10_STRIPS, VK_PASS_SP };
+enum { VK_PLAN_COUPLED = 1, VK_PLAN_COUPLED_AGENTS = 2 };
+typedef struct vk_pass {
+    int32_t k, src, dst, f0;
+    int32_t lo, hi, in_lo, in_hi, gap_lo, gap_hi;
+    int32_t kernel, couple, copy_back;
+} vk_pass;
+int vk_diffuse_plan(int32_t row_lo, int32_t row_hi, int32_t lo_min, int32_t hi_max, int32_t edge_top,
+                    int32_t edge_bot, int32_t sub_begin, int32_t sub_count, int32_t n_sub, int32_t part,
+                    int32_t interior_passes, int32_t coupled, vk_pass *out, int32_t capacity,
+                    int32_t *n_passes);
+
 /* Maximum substeps fused per HBM pass by vk_diffuse (temporal blocking; odd,
  * 1..15; 1 = one launch per substep; or 10, the default: a block of a multiple
  * of 10 substeps as 10-deep passes -- in the tolerance mode over three buffers

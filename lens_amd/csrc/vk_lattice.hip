@@ -25,6 +25,7 @@
 
 #include "vk_bin.h"
 #include "vk_internal.h"
+#include "vk_pass_plan.h"
 #include "vk_stencil_launch.h"
 
 constexpr int ST_BX = 256;  // columns per block (4 waves, 2 KiB per row load)
@@ -76,7 +77,7 @@ __global__ __launch_bounds__(ST_BX) void k_diffuse_substep(const double *__restr
     }
 }
 
-int g_stencil_rows = 0;    // output rows per wave tile (vk_stencil_kernels.h chunk_rows); 0 = auto
+static int g_stencil_rows = 0;    // output rows per wave tile (vk_stencil_kernels.h chunk_rows); 0 = auto
 // Exact mode: 2 / 3 = wave tile lag-1 prefetching 3 / 6 rows, 6 = variant 3 with
 // streaming stores at depths 7 / 9 / 11 (the exact mode's kernel for every other
 // setting).  Tolerance mode: 20 = pair-sum passes (vk_stencil_ps.h, the default; 2 /
@@ -106,7 +107,7 @@ extern "C" int vk_set_stencil_kernel(int32_t variant, int32_t rows) {
 // pair-sum passes (3 FP64 ops per cell-substep instead of 6, vk_stencil_ps.h) and no
 // base re-read in the final pass; fields agree with the exact mode to ~1e-14
 // relative (tests/test_stencil_modes.py)
-int g_stencil_mode = 0;
+static int g_stencil_mode = 0;
 
 extern "C" int vk_set_stencil_mode(int32_t mode) {
     const int prev = g_stencil_mode;
@@ -185,81 +186,80 @@ __global__ __launch_bounds__(256) void k_copy_rows(const double *__restrict__ sr
         dst[base + i] = src[base + i];
 }
 
-// One fused pass of k >= 2 substeps, the kernel picked by mode / variant / depth;
-// f0 != nullptr marks the exact mode's final pass (it re-reads the step-start plane).
-// cp (nullable): the agent coupling the pass carries (vk_diffuse_coupled).
-static void launch_pass(int k, hipStream_t s, const double *src, double *dst, const double *f0, int nf, int64_t fs,
-                        int ny, int lo, int hi, int in_lo, int in_hi, int top, int bot, double coef, const double *mm,
-                        const VkPsCouple *cp, bool strip = false) {
-    if (g_stencil_mode == 1 && k <= 11 && ((k & 1) || k == 10)) {
-        // tolerance mode, pair-sum passes (the final pass writes the new field as is);
-        // they are instantiated for k = 3, 5, 7, 9, 10, 11 (an even k < 10 takes the
-        // wave tiles below); variant 40: the stage-split 10-deep pass -- not for the
-        // short edge strips of vk_diffuse_part (`strip`), whose passes are latency-bound
-        // and run faster as single-wave tiles of a few rows
-        if (g_stencil_kernel >= 40 && !strip &&
-            vk_launch_sp(g_stencil_kernel, k, s, src, dst, f0, nf, fs, ny, lo, hi, in_lo, in_hi, top, bot, coef, mm, cp))
-            return;
-        if (k == 10 && g_stencil_kernel == 70 && !strip)
-            vk_launch_ps10_aligned(k, s, src, dst, f0, nf, fs, ny, lo, hi, in_lo, in_hi, top, bot, coef, mm, cp);
-        else if (k == 10) vk_launch_ps10(k, s, src, dst, f0, nf, fs, ny, lo, hi, in_lo, in_hi, top, bot, coef, mm, cp);
-        else vk_launch_ps(k, s, src, dst, f0, nf, fs, ny, lo, hi, in_lo, in_hi, top, bot, coef, mm, cp);
-    } else if (k == 10 || ((g_stencil_kernel == 6 || g_stencil_kernel >= 20) && (k == 7 || k == 9 || k == 11))) {
-        // the exact mode's variant 6 (streaming stores), and its 10-deep whole-step plan
-        vk_launch_wl6nt(k, s, src, dst, f0, nf, fs, ny, lo, hi, in_lo, in_hi, top, bot, coef, mm, cp);
+// ---------------------------------------------------------------------------
+// vk_diffuse / vk_diffuse_part / vk_diffuse_coupled: validate, plan
+// (vk_pass_plan.h), launch each pass of the plan
+// ---------------------------------------------------------------------------
+
+static vk_plan::Settings stencil_settings() {
+    return {g_stencil_mode, g_stencil_depth, g_stencil_kernel, g_stencil_rows};
+}
+
+// What a call's passes share: the three buffers (indexed by VK_BUF_*), the planes,
+// the reflected rows, the coefficient; cp (nullable): the agent coupling of a
+// coupled step, of which each pass carries its own bits.
+struct PassArgs {
+    double *buf[3];
+    int nf;
+    int64_t fs;
+    int ny, top, bot, tile_rows;
+    double coef;
+    const double *uniform;
+    const VkPsCouple *cp;
+    hipStream_t stream;
+};
+
+static void launch_pass(const vk_pass &p, const PassArgs &a) {
+    typedef void (*launcher)(VK_STENCIL_LAUNCH_ARGS);
+    static const launcher launchers[] = {nullptr,        vk_launch_wl3,  vk_launch_wl6,          vk_launch_wl6nt,
+                                         vk_launch_ps,   vk_launch_ps10, vk_launch_ps10_aligned, nullptr,
+                                         vk_launch_sp};
+    const double *src = a.buf[p.src], *f0 = p.f0 ? a.buf[VK_BUF_FIELD] : nullptr;
+    double *dst = a.buf[p.dst];
+    VkPsCouple c = {};
+    if (a.cp) c = *a.cp, c.mode = p.couple;
+    const VkPsCouple *cp = a.cp ? &c : nullptr;
+    if (p.kernel == VK_PASS_SINGLE) {
+        dim3 grid((a.ny + ST_BX - 1) / ST_BX, (p.hi - p.lo + ST_RB - 1) / ST_RB, a.nf);
+        hipLaunchKernelGGL(k_diffuse_substep, grid, dim3(ST_BX), 0, a.stream, src, dst, f0, a.fs, a.ny, p.lo, p.hi, a.top,
+                           a.bot, a.coef, a.uniform, 0);
+    } else if (p.kernel == VK_PASS_PS10_STRIPS) {
+        vk_launch_ps10_strips(p.k, a.stream, src, dst, f0, a.nf, a.fs, a.ny, p.lo, p.hi, p.in_lo, p.in_hi, a.top, a.bot,
+                              a.coef, a.uniform, cp, a.tile_rows, p.gap_lo, p.gap_hi);
     } else {
-        // other depths (and variants 2 / 3): the plain-store wave tiles; the final pass
-        // also streams the base plane (3 rows ahead), so it keeps the shallow row
-        // prefetch and still fits 3 waves per SIMD
-        auto launch = (g_stencil_kernel == 2 || f0) ? vk_launch_wl3 : vk_launch_wl6;
-        launch(k, s, src, dst, f0, nf, fs, ny, lo, hi, in_lo, in_hi, top, bot, coef, mm, cp);
+        launchers[p.kernel](p.k, a.stream, src, dst, f0, a.nf, a.fs, a.ny, p.lo, p.hi, p.in_lo, p.in_hi, a.top, a.bot,
+                            a.coef, a.uniform, cp, a.tile_rows);
     }
 }
 
-// The odd-depth pass plan of a call's substeps [sub_begin, last]: the fewest odd
-// depths <= the set depth that sum to the count (a sum of P odd numbers has the
-// parity of P), as even as possible -- e.g. 100 = 8x9 + 4x7 rather than 11x9 + a
-// lone single-substep pass.
-static std::vector<int> odd_plan(int sub_count) {
-    int depth = g_stencil_depth | 1;   // odd
-    if (g_stencil_depth == 10) depth = 9;
-    if (depth > 15) depth = 15;
-    int passes = (sub_count + depth - 1) / depth;
-    if ((passes & 1) != (sub_count & 1)) ++passes;
-    std::vector<int> ks;
-    for (int j = 0, left = passes; j < sub_count; --left) {
-        const int rem = sub_count - j;   // rem has the parity of `left`
-        int k = (rem + left - 1) / left;
-        if ((k & 1) == 0) ++k;
-        if (k > depth) k = depth;
-        while (k > 1 && rem - k < left - 1) k -= 2;
-        ks.push_back(k);
-        j += k;
+// Plans the call and launches its passes.  Uniform planes skip every pass (nothing
+// reads the buffers they leave unwritten) and keep their field.
+static int run_plan(const char *what, const vk_plan::Call &c, double *field, double *work0, double *work1, int32_t n_fields,
+                    int64_t field_stride, int32_t ny, double coeff_dt, const double *uniform, const VkPsCouple *cp,
+                    vk_stream_t stream) {
+    const vk_plan::Settings st = stencil_settings();
+    std::vector<vk_pass> passes;
+    const char *why = "";
+    int rc = vk_plan::plan(st, c, passes, &why);
+    if (rc) {
+        vk::set_error("%s: %s", what, why);
+        return rc;
     }
-    return ks;
-}
-
-static int diffuse_impl(double *field, double *work0, double *work1, int32_t n_fields, int64_t field_stride,
-                        int32_t ny, int32_t row_lo, int32_t row_hi, int32_t lo_min, int32_t hi_max, int32_t edge_top,
-                        int32_t edge_bot, int32_t sub_begin, int32_t sub_count, int32_t n_sub, double coeff_dt,
-                        const double *uniform, int32_t part, int32_t split_m, vk_stream_t stream);
-
-extern "C" int vk_diffuse(double *field, double *work0, double *work1, int32_t n_fields,
-                          int64_t field_stride, int32_t ny, int32_t row_lo, int32_t row_hi, int32_t lo_min,
-                          int32_t hi_max, int32_t edge_top, int32_t edge_bot, int32_t sub_begin,
-                          int32_t sub_count, int32_t n_sub, double coeff_dt, const double *uniform,
-                          vk_stream_t stream) {
-    return diffuse_impl(field, work0, work1, n_fields, field_stride, ny, row_lo, row_hi, lo_min, hi_max, edge_top,
-                        edge_bot, sub_begin, sub_count, n_sub, coeff_dt, uniform, VK_PART_ALL, 0, stream);
-}
-
-// Whether vk_diffuse_part can split this block: the 10-deep plan of a row band's
-// block of 10 k substeps whose owned rows keep an interior through every pass.
-static bool part_plan_ok(int32_t row_lo, int32_t row_hi, int32_t lo_min, int32_t hi_max, int32_t sub_count,
-                         int32_t edge_top, int32_t edge_bot) {
-    const bool halo_top = !edge_top && row_lo > lo_min, halo_bot = !edge_bot && row_hi < hi_max;
-    return g_stencil_depth == 10 && sub_count % 10 == 0 && sub_count > 0 && (halo_top || halo_bot) &&
-           row_hi - row_lo > 2 * sub_count;
+    if (n_fields == 0) return VK_OK;
+    const PassArgs a = {{field, work0, work1}, n_fields, field_stride, ny, c.edge_top ? c.lo_min : -1,
+                        c.edge_bot ? c.hi_max - 1 : 0x7fffffff, st.rows, coeff_dt, uniform, cp, (hipStream_t)stream};
+    for (const vk_pass &p : passes) {
+        launch_pass(p, a);
+        if ((rc = vk::launch_check(what))) return rc;
+        if (p.copy_back) {
+            const int64_t count = (int64_t)(c.row_hi - c.row_lo) * ny;
+            const unsigned blocks = (unsigned)std::min<int64_t>(2048, (count + 255) / 256);
+            hipLaunchKernelGGL(k_copy_rows, dim3(blocks, n_fields), dim3(256), 0, a.stream, work0, field, field_stride,
+                               (int64_t)c.row_lo * ny, count, uniform);
+            if ((rc = vk::launch_check("k_copy_rows"))) return rc;
+        }
+    }
+    return VK_OK;
 }
 
 extern "C" int vk_diffuse_part(double *field, double *work0, double *work1, int32_t n_fields, int64_t field_stride,
@@ -267,25 +267,13 @@ extern "C" int vk_diffuse_part(double *field, double *work0, double *work1, int3
                                int32_t edge_top, int32_t edge_bot, int32_t sub_begin, int32_t sub_count,
                                int32_t n_sub, double coeff_dt, const double *uniform, int32_t part,
                                int32_t interior_passes, vk_stream_t stream) {
+    const vk_plan::Call c = {row_lo,    row_hi,    lo_min, hi_max, edge_top,        edge_bot,
+                             sub_begin, sub_count, n_sub,  part,   interior_passes, 0};
     if (part != VK_PART_ALL && part != VK_PART_INTERIOR && part != VK_PART_EDGES) {
         vk::set_error("vk_diffuse_part: part must be VK_PART_ALL / _INTERIOR / _EDGES");
         return VK_ERR_ARG;
     }
-    if (part != VK_PART_ALL && !part_plan_ok(row_lo, row_hi, lo_min, hi_max, sub_count, edge_top, edge_bot)) {
-        vk::set_error("vk_diffuse_part: the block is not a 10-deep-plan band block with an interior");
-        return VK_ERR_LIMIT;
-    }
-    return diffuse_impl(field, work0, work1, n_fields, field_stride, ny, row_lo, row_hi, lo_min, hi_max, edge_top,
-                        edge_bot, sub_begin, sub_count, n_sub, coeff_dt, uniform, part, interior_passes, stream);
-}
-
-static int diffuse_impl(double *field, double *work0, double *work1, int32_t n_fields, int64_t field_stride,
-                        int32_t ny, int32_t row_lo, int32_t row_hi, int32_t lo_min, int32_t hi_max, int32_t edge_top,
-                        int32_t edge_bot, int32_t sub_begin, int32_t sub_count, int32_t n_sub, double coeff_dt,
-                        const double *uniform, int32_t part, int32_t split_m, vk_stream_t stream) {
-    if (!field || n_fields < 0 || ny <= 0 || row_lo < lo_min || row_hi > hi_max || row_lo >= row_hi ||
-        sub_begin < 0 || sub_count < 0 || sub_begin + sub_count > n_sub ||
-        (int64_t)hi_max * ny > field_stride) {
+    if (!field || n_fields < 0 || ny <= 0 || !vk_plan::geometry_ok(c) || (int64_t)hi_max * ny > field_stride) {
         vk::set_error("vk_diffuse: bad geometry");
         return VK_ERR_ARG;
     }
@@ -293,147 +281,38 @@ static int diffuse_impl(double *field, double *work0, double *work1, int32_t n_f
         vk::set_error("vk_diffuse: work buffers required");
         return VK_ERR_ARG;
     }
-    if (n_fields == 0 || sub_count == 0) return VK_OK;
-    // The state after substep j lives in work[j & 1] (field after the last
-    // substep).  A pass of k substeps [j, j+k) reads work[(j-1)&1] (field for
-    // j == 0) and writes work[(j+k-1)&1]; k is kept ODD so the two differ.
-    double *work[2] = {work0, work1};
-    const int top_reflect = edge_top ? lo_min : -1;
-    const int bot_reflect = edge_bot ? hi_max - 1 : 0x7fffffff;
-    hipStream_t s = (hipStream_t)stream;
-    const int last_in_call = sub_begin + sub_count - 1;
-    if (g_stencil_depth == 10 && sub_count % 10 == 0 && work1) {
-        // A block of 10 k substeps: k passes of 10.  In the tolerance mode the final
-        // pass writes the field without reading it back (no f0), so when the block ends
-        // the step the field is a third buffer (its step-start values are not needed
-        // once the first pass has read them).  The exact mode's final pass re-reads the
-        // step-start field (f0 + (f - f0), in place like the odd-depth plan's), so there
-        // the field is never scratch.  The block starts in the buffer the odd-depth
-        // convention holds the state in (field for substep 0, else work[(j-1)&1]) and
-        // ends in the one it expects after the block (field after the last substep,
-        // else work[last & 1]), so halo exchanges between blocks (row bands) see the
-        // usual buffers.  Buffers are assigned backwards from the target: each pass
-        // writes one its source is not (a block inside the step starts and ends in the
-        // same work buffer, so it needs an even number of passes; otherwise it takes
-        // the odd-depth plan below).  Uniform planes skip every pass (nothing reads
-        // the buffers they leave unwritten) and keep their field.
-        const int P = sub_count / 10;
-        const bool ends_step = last_in_call == n_sub - 1;
-        double *S = sub_begin == 0 ? field : work[(sub_begin - 1) & 1];
-        double *T = ends_step ? field : work[last_in_call & 1];
-        double *cand[3] = {work0, work1, field};
-        // the field is scratch only in a tolerance-mode block that ends the step
-        const int nc = (ends_step && g_stencil_mode == 1) ? 3 : 2;
-        double *dsts[64];
-        bool ok = P >= 1 && P <= 64;
-        for (int p = P - 1; ok && p >= 0; --p) {
-            if (p == P - 1) {
-                dsts[p] = T;
-            } else {
-                dsts[p] = nullptr;
-                for (int c = 0; c < nc && !dsts[p]; ++c)
-                    if (cand[c] != dsts[p + 1] && (p > 0 || cand[c] != S)) dsts[p] = cand[c];
-                ok = dsts[p] != nullptr;
-            }
-        }
-        ok = ok && dsts[0] != S;
-        if (ok) {
-            // part (vk_diffuse_part): the interior of pass p is the rows whose inputs at
-            // the block's start are all owned -- [row_lo + 10 (p+1), row_hi - 10 (p+1)) on
-            // a side with halo rows -- and the edges are the rest of the pass's rows.
-            // The interior passes read and write only interior rows of each buffer, the
-            // edge passes read at most 20 rows into the interior of the pass before, which
-            // no later interior pass writes (it starts 10 rows deeper per pass), so the
-            // interior of the first m passes can run before any edge pass (while the halo
-            // arrives).  Then (part EDGES) the edges of those m passes, and the remaining
-            // passes whole.
-            const bool halo_top = !edge_top && row_lo > lo_min, halo_bot = !edge_bot && row_hi < hi_max;
-            const int m = (split_m <= 0 || split_m > P) ? P : split_m;
-            for (int p = 0; p < P; ++p) {
-                if (part == VK_PART_INTERIOR && p >= m) break;
-                const int e = sub_begin + 10 * p + 9;
-                const int grow = last_in_call - e;
-                const int lo = max(lo_min, row_lo - grow);
-                const int hi = min(hi_max, row_hi + grow);
-                const double *f0 = (g_stencil_mode != 1 && ends_step && p == P - 1) ? field : nullptr;
-                const int ilo = halo_top ? row_lo + 10 * (p + 1) : lo;
-                const int ihi = halo_bot ? row_hi - 10 * (p + 1) : hi;
-                int ranges[3][2];
-                int nr = 0;
-                const bool strip = part == VK_PART_EDGES && p < m;
-                if (part == VK_PART_ALL || (part == VK_PART_EDGES && p >= m)) {
-                    ranges[nr][0] = lo, ranges[nr][1] = hi, ++nr;
-                } else if (part == VK_PART_INTERIOR) {
-                    ranges[nr][0] = ilo, ranges[nr][1] = ihi, ++nr;
-                } else if (halo_top && halo_bot && ilo < ihi && g_stencil_mode == 1) {
-                    // both strips as one launch (pair-sum pass with a row gap)
-                    const int in_lo = max(lo_min, lo - 10), in_hi = min(hi_max, hi + 10);
-                    vk_launch_ps10_strips(10, s, p ? dsts[p - 1] : S, dsts[p], f0, n_fields, field_stride, ny, lo, hi,
-                                          in_lo, in_hi, top_reflect, bot_reflect, coeff_dt, uniform, nullptr, ilo, ihi);
-                    int rc = vk::launch_check("vk_diffuse kernel (depth 10, edge strips)");
-                    if (rc) return rc;
-                } else {
-                    if (halo_top) ranges[nr][0] = lo, ranges[nr][1] = ilo, ++nr;
-                    if (halo_bot) ranges[nr][0] = ihi, ranges[nr][1] = hi, ++nr;
-                }
-                for (int q = 0; q < nr; ++q) {
-                    const int olo = ranges[q][0], ohi = ranges[q][1];
-                    if (olo >= ohi) continue;
-                    const int in_lo = max(lo_min, olo - 10), in_hi = min(hi_max, ohi + 10);
-                    launch_pass(10, s, p ? dsts[p - 1] : S, dsts[p], f0, n_fields, field_stride, ny, olo, ohi, in_lo,
-                                in_hi, top_reflect, bot_reflect, coeff_dt, uniform, nullptr, strip);
-                    int rc = vk::launch_check("vk_diffuse kernel (depth 10)");
-                    if (rc) return rc;
-                }
-            }
-            return VK_OK;
-        }
-        if (part != VK_PART_ALL) {
-            vk::set_error("vk_diffuse_part: no 10-deep buffer plan for this block");
-            return VK_ERR_LIMIT;
-        }
+    return run_plan("vk_diffuse", c, field, work0, work1, n_fields, field_stride, ny, coeff_dt, uniform, nullptr, stream);
+}
+
+extern "C" int vk_diffuse(double *field, double *work0, double *work1, int32_t n_fields,
+                          int64_t field_stride, int32_t ny, int32_t row_lo, int32_t row_hi, int32_t lo_min,
+                          int32_t hi_max, int32_t edge_top, int32_t edge_bot, int32_t sub_begin,
+                          int32_t sub_count, int32_t n_sub, double coeff_dt, const double *uniform,
+                          vk_stream_t stream) {
+    return vk_diffuse_part(field, work0, work1, n_fields, field_stride, ny, row_lo, row_hi, lo_min, hi_max, edge_top,
+                           edge_bot, sub_begin, sub_count, n_sub, coeff_dt, uniform, VK_PART_ALL, 0, stream);
+}
+
+extern "C" int vk_diffuse_plan(int32_t row_lo, int32_t row_hi, int32_t lo_min, int32_t hi_max, int32_t edge_top,
+                               int32_t edge_bot, int32_t sub_begin, int32_t sub_count, int32_t n_sub, int32_t part,
+                               int32_t interior_passes, int32_t coupled, vk_pass *out, int32_t capacity,
+                               int32_t *n_passes) {
+    const vk_plan::Call c = {row_lo,    row_hi,    lo_min, hi_max, edge_top,        edge_bot,
+                             sub_begin, sub_count, n_sub,  part,   interior_passes, coupled};
+    const bool whole_step = row_lo == 0 && lo_min == 0 && row_hi == hi_max && sub_begin == 0 && sub_count == n_sub &&
+                            part == VK_PART_ALL;
+    if (!n_passes || capacity < 0 || (capacity > 0 && !out) || part < VK_PART_ALL || part > VK_PART_EDGES ||
+        coupled < 0 || coupled > VK_PLAN_COUPLED_AGENTS || (coupled && !whole_step) || !vk_plan::geometry_ok(c)) {
+        vk::set_error("vk_diffuse_plan: bad arguments");
+        return VK_ERR_ARG;
     }
-    if (part != VK_PART_ALL) {
-        vk::set_error("vk_diffuse_part: only the 10-deep plan splits");
-        return VK_ERR_LIMIT;
-    }
-    const std::vector<int> ks = odd_plan(sub_count);
-    int j = sub_begin;
-    for (size_t p = 0; p < ks.size(); ++p) {
-        const int k = ks[p];
-        const int e = j + k - 1;     // last substep of this pass
-        const int grow = last_in_call - e;
-        const int lo = max(lo_min, row_lo - grow);
-        const int hi = min(hi_max, row_hi + grow);
-        const int in_lo = max(lo_min, lo - k), in_hi = min(hi_max, hi + k);
-        const double *src = (j == 0) ? field : work[(j - 1) & 1];
-        const bool final_pass = (e == n_sub - 1);
-        // a pass that both starts from and ends in `field` cannot run in place
-        // (neighbours would read new values): it goes through work0 + copy
-        const bool in_place = final_pass && j == 0;
-        double *dst = (final_pass && !in_place) ? field : (in_place ? work0 : work[e & 1]);
-        const double *f0 = final_pass ? field : nullptr;
-        if (k == 1) {
-            dim3 grid((ny + ST_BX - 1) / ST_BX, (hi - lo + ST_RB - 1) / ST_RB, n_fields);
-            hipLaunchKernelGGL(k_diffuse_substep, grid, dim3(ST_BX), 0, s, src, dst, f0, field_stride, ny, lo,
-                               hi, top_reflect, bot_reflect, coeff_dt, uniform, 0);
-        } else {
-            launch_pass(k, s, src, dst, f0, n_fields, field_stride, ny, lo, hi, in_lo, in_hi, top_reflect, bot_reflect,
-                        coeff_dt, uniform, nullptr);
-        }
-        int rc = vk::launch_check("vk_diffuse kernel");
-        if (rc) return rc;
-        if (in_place) {
-            const int64_t count = (int64_t)(row_hi - row_lo) * ny;
-            const unsigned blocks = (unsigned)std::min<int64_t>(2048, (count + 255) / 256);
-            hipLaunchKernelGGL(k_copy_rows, dim3(blocks, n_fields), dim3(256), 0, s, work0, field, field_stride,
-                               (int64_t)row_lo * ny, count, uniform);
-            rc = vk::launch_check("k_copy_rows");
-            if (rc) return rc;
-        }
-        j += k;
-    }
-    return VK_OK;
+    std::vector<vk_pass> passes;
+    const char *why = "";
+    const int rc = vk_plan::plan(stencil_settings(), c, passes, &why);
+    if (rc) vk::set_error("vk_diffuse_plan: %s", why);
+    *n_passes = (int32_t)passes.size();
+    std::copy_n(passes.begin(), std::min<size_t>(passes.size(), (size_t)capacity), out);
+    return rc;
 }
 
 // A whole-plane step's passes with the agent coupling inside them: the first
@@ -466,51 +345,22 @@ extern "C" int vk_diffuse_coupled(double *field, double *work0, double *work1, i
     cp.counts = counts;
     cp.cld = counts_ld;
     cp.bva = binvol_avogadro;
-    if (n_fields <= VK_COUPLE_MAX_FIELDS) {
-        for (int f = 0; f < n_fields; ++f) {
-            if (gather_row[f] >= 127 || count_row[f] >= 127 || (gather_row[f] >= 0 && (!conc || conc_ld < n_agents)) ||
-                (count_row[f] >= 0 && (!counts || counts_ld < n_agents))) {
-                vk::set_error("vk_diffuse_coupled: bad gather / count rows");
-                return VK_ERR_ARG;
-            }
-            cp.grow[f] = (int8_t)(gather_row[f] < 0 ? -1 : gather_row[f]);
-            cp.crow[f] = (int8_t)(count_row[f] < 0 ? -1 : count_row[f]);
+    if (n_fields > VK_COUPLE_MAX_FIELDS) {
+        vk::set_error("vk_diffuse_coupled: at most 8 planes");
+        return VK_ERR_LIMIT;
+    }
+    for (int f = 0; f < n_fields; ++f) {
+        if (gather_row[f] >= 127 || count_row[f] >= 127 || (gather_row[f] >= 0 && (!conc || conc_ld < n_agents)) ||
+            (count_row[f] >= 0 && (!counts || counts_ld < n_agents))) {
+            vk::set_error("vk_diffuse_coupled: bad gather / count rows");
+            return VK_ERR_ARG;
         }
+        cp.grow[f] = (int8_t)(gather_row[f] < 0 ? -1 : gather_row[f]);
+        cp.crow[f] = (int8_t)(count_row[f] < 0 ? -1 : count_row[f]);
     }
-    // the plan: vk_diffuse's (10-deep passes in the tolerance mode's depth-10 setting,
-    // else odd depths), at least two fused passes (the gather rides on the first, the
-    // exchange on the last) and no single-substep pass
-    if (n_fields > VK_COUPLE_MAX_FIELDS || n_sub < 2) {
-        vk::set_error("vk_diffuse_coupled: at most 8 planes and 2 substeps");
-        return VK_ERR_LIMIT;
-    }
-    const bool ten = g_stencil_depth == 10 && g_stencil_mode == 1 && n_sub % 10 == 0 && n_sub >= 20;
-    std::vector<int> ks = ten ? std::vector<int>(n_sub / 10, 10) : odd_plan(n_sub);
-    bool ok = ks.size() >= 2;
-    for (int k : ks) ok = ok && k >= 2;
-    if (!ok) {
-        vk::set_error("vk_diffuse_coupled: the step is not planned as two or more fused passes");
-        return VK_ERR_LIMIT;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const int np = (int)ks.size();
-    const double *cur = field;
-    for (int p = 0, j = 0; p < np; j += ks[p], ++p) {
-        const bool last = p == np - 1;
-        double *dst;
-        if (last) dst = field;
-        else if (ten) dst = cur == work0 ? work1 : work0;
-        else dst = (j + ks[p] - 1) & 1 ? work1 : work0;   // work[e & 1], e = this pass's last substep
-        VkPsCouple c = cp;
-        c.mode = n_agents > 0 ? (p == 0 ? 1 : 0) | (last ? 2 : 0) : 0;
-        // the exact mode's final pass re-reads the step-start plane: vk_diffuse's f0
-        launch_pass(ks[p], s, cur, dst, last ? field : nullptr, n_fields, field_stride, ny, 0, rows, 0, rows, 0,
-                    rows - 1, coeff_dt, uniform, &c);
-        const int rc = vk::launch_check("vk_diffuse_coupled kernel");
-        if (rc) return rc;
-        cur = dst;
-    }
-    return VK_OK;
+    const vk_plan::Call c = {0, rows, 0, rows, 1, 1, 0, n_sub, n_sub, VK_PART_ALL, 0,
+                             n_agents > 0 ? VK_PLAN_COUPLED_AGENTS : VK_PLAN_COUPLED};
+    return run_plan("vk_diffuse_coupled", c, field, work0, work1, n_fields, field_stride, ny, coeff_dt, uniform, &cp, stream);
 }
 
 extern "C" int vk_diffuse_delta(double *field, double *work0, double *work1, double *delta, int32_t n_fields,

@@ -361,11 +361,11 @@ __global__ __launch_bounds__(256) VK_WL_WAVES_ATTR void k_diffuse_wl(VK_WL_PARAM
     diffuse_wl_tile<K, PD, FINAL>(VK_WL_ARGS);
 }
 
-// Rows per wave tile: g_stencil_rows, or (auto) by the height of the rows the
+// Rows per wave tile: the set rows (vk_set_stencil_kernel), or (auto) by the height of the rows the
 // pass writes -- small row bands (multi-GPU strong scaling) trade pipeline
 // fill for more waves.
-static int chunk_rows(int out_rows, int tiles_x, int nf) {
-    if (::g_stencil_rows > 0) return ::g_stencil_rows;
+static int chunk_rows(int tile_rows, int out_rows, int tiles_x, int nf) {
+    if (tile_rows > 0) return tile_rows;
     // auto: the strong-scaling sweep of 4096^2 x 2 bands (scripts/halo_sweep.py,
     // profiles/r02_halo_sweep/) is fastest with 64-row tiles on the whole
     // plane, 32 on 1/2 and 1/4 bands, 16 on 1/8 bands.  Narrower lattices have

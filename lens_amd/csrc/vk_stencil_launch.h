@@ -1,6 +1,8 @@
 // Launchers of the fused-pass stencil kernels (vk_stencil_*.hip), called by
-// vk_diffuse (vk_lattice.hip).  k = substeps fused in the pass (odd, 3..15);
-// f0 != nullptr marks the FINAL pass (writes f0 + (f - f0)).
+// vk_diffuse (vk_lattice.hip) for the passes of its plan (vk_pass_plan.h).  k =
+// substeps fused in the pass (odd 3..15, or 10); f0 != nullptr marks the FINAL pass
+// (writes f0 + (f - f0)); tile_rows = output rows per wave tile, 0 = auto
+// (vk_set_stencil_kernel).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,10 +11,7 @@
 #define VK_STENCIL_LAUNCH_ARGS                                                                                 \
     int k, hipStream_t st, const double *src, double *dst, const double *f0, int nf, int64_t fs, int ny,        \
         int out_lo, int out_hi, int in_lo, int in_hi, int top, int bot, double coef, const double *mm,          \
-        const struct VkPsCouple *cp
-
-extern int g_stencil_rows;   // output rows per wave tile, 0 = auto (vk_lattice.hip, vk_set_stencil_kernel)
-extern int g_stencil_mode;   // 0 = bit-exact (default), 1 = tolerance / FMA (vk_set_stencil_mode)
+        const struct VkPsCouple *cp, int tile_rows
 
 struct VkPsCouple;
 void vk_launch_wl3(VK_STENCIL_LAUNCH_ARGS);          // lag-1 wave tile, 3 rows prefetched
@@ -42,7 +41,7 @@ void vk_launch_ps(VK_STENCIL_LAUNCH_ARGS);     // tolerance mode, pair-sum form 
 void vk_launch_ps10(VK_STENCIL_LAUNCH_ARGS);   // the same, k = 10
 void vk_launch_ps10_strips(VK_STENCIL_LAUNCH_ARGS, int gap_lo, int gap_hi);   // k = 10, two strips
 void vk_launch_ps10_aligned(VK_STENCIL_LAUNCH_ARGS);   // k = 10, 96 written columns (variant 70)
-bool vk_launch_sp(int variant, VK_STENCIL_LAUNCH_ARGS);       // variant 40-43 (k = 10); false: not taken
+void vk_launch_sp(VK_STENCIL_LAUNCH_ARGS);             // the stage-split pass (variant 40): k = 10, no coupling
 
 // ---------------------------------------------------------------------------
 // Agent coupling inside a pass (vk_diffuse_coupled), shared by both kernel

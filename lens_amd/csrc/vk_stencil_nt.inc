@@ -9,13 +9,13 @@ namespace {
 template <int K, int PD>
 void launch(hipStream_t st, const double *src, double *dst, const double *f0, int nf, int64_t fs, int ny,
             int out_lo, int out_hi, int in_lo, int in_hi, int top, int bot, double coef, const double *mm,
-            const VkPsCouple *cp) {
+            const VkPsCouple *cp, int tile_rows) {
     VkPsCouple none = {};
     const VkPsCouple &c = cp ? *cp : none;
     constexpr int KH = K + (K & 1);
     constexpr int W = WT_COLS - 2 * KH;
     const int tiles_x = (ny + W - 1) / W;
-    const int rch = chunk_rows(out_hi - out_lo, tiles_x, nf);
+    const int rch = chunk_rows(tile_rows, out_hi - out_lo, tiles_x, nf);
     const int chunks_y = (out_hi - out_lo + rch - 1) / rch;
     const int waves = tiles_x * chunks_y * nf;
     int ea = 0, eb = 0;

@@ -355,13 +355,13 @@ __global__ __launch_bounds__(256) void k_diffuse_ps(const double *__restrict__ s
 template <int K, int PD, int C, int CP = 0, int KHO = 0>
 void launch(hipStream_t st, const double *src, double *dst, int nf, int64_t fs, int ny, int out_lo, int out_hi,
             int in_lo, int in_hi, int top, int bot, double coef, const double *mm, const VkPsCouple *cp,
-            int gap_lo = -1, int gap_hi = -1) {
+            int tile_rows, int gap_lo = -1, int gap_hi = -1) {
     constexpr int KH = KHO > 0 ? KHO : (K + C - 1) / C * C;
     constexpr int W = 64 * C - 2 * KH;
     const int tiles_x = (ny + W - 1) / W;
     if (!(gap_lo >= out_lo && gap_lo <= gap_hi && gap_hi <= out_hi)) gap_lo = gap_hi = out_hi;
     const int rows_a = gap_lo - out_lo, rows_b = out_hi - gap_hi;
-    const int rch = chunk_rows(rows_a + rows_b, tiles_x, nf);
+    const int rch = chunk_rows(tile_rows, rows_a + rows_b, tiles_x, nf);
     const int chunks_a = (rows_a + rch - 1) / rch;
     const int chunks_y = chunks_a + (rows_b + rch - 1) / rch;
     const int waves = tiles_x * chunks_y * nf;

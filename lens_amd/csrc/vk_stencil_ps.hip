@@ -5,7 +5,7 @@
 // variant 20: 2 columns per lane, 4 rows prefetched
 void vk_launch_ps(VK_STENCIL_LAUNCH_ARGS) {
     (void)f0;   // the tolerance mode's final pass writes the new field as is
-#define VK_PS(KC) case KC: vk_ps::launch<KC, 4, 2>(st, src, dst, nf, fs, ny, out_lo, out_hi, in_lo, in_hi, top, bot, coef, mm, cp); break
+#define VK_PS(KC) case KC: vk_ps::launch<KC, 4, 2>(st, src, dst, nf, fs, ny, out_lo, out_hi, in_lo, in_hi, top, bot, coef, mm, cp, tile_rows); break
     switch (k) {
         VK_PS(3); VK_PS(5); VK_PS(7); VK_PS(9); VK_PS(11);
         default: vk::set_error("vk_launch_ps: no pair-sum pass of depth %d", k); break;

@@ -12,9 +12,9 @@ void vk_launch_ps10(VK_STENCIL_LAUNCH_ARGS) {
     (void)f0; (void)k;
     const double pass_bytes = 16.0 * (double)(in_hi - in_lo) * (double)ny * (double)nf;
     if (pass_bytes <= 192.0 * 1024 * 1024)
-        vk_ps::launch<10, 4, 2, 2>(st, src, dst, nf, fs, ny, out_lo, out_hi, in_lo, in_hi, top, bot, coef, mm, cp);
+        vk_ps::launch<10, 4, 2, 2>(st, src, dst, nf, fs, ny, out_lo, out_hi, in_lo, in_hi, top, bot, coef, mm, cp, tile_rows);
     else
-        vk_ps::launch<10, 4, 2>(st, src, dst, nf, fs, ny, out_lo, out_hi, in_lo, in_hi, top, bot, coef, mm, cp);
+        vk_ps::launch<10, 4, 2>(st, src, dst, nf, fs, ny, out_lo, out_hi, in_lo, in_hi, top, bot, coef, mm, cp, tile_rows);
 }
 
 // Both edge strips of a band's 10-deep pass in one launch (vk_diffuse_part): rows
@@ -22,8 +22,8 @@ void vk_launch_ps10(VK_STENCIL_LAUNCH_ARGS) {
 // so a pass is latency-bound, and one launch costs about what one strip did.
 void vk_launch_ps10_strips(VK_STENCIL_LAUNCH_ARGS, int gap_lo, int gap_hi) {
     (void)f0; (void)k;
-    vk_ps::launch<10, 4, 2, 2>(st, src, dst, nf, fs, ny, out_lo, out_hi, in_lo, in_hi, top, bot, coef, mm, cp, gap_lo,
-                               gap_hi);
+    vk_ps::launch<10, 4, 2, 2>(st, src, dst, nf, fs, ny, out_lo, out_hi, in_lo, in_hi, top, bot, coef, mm, cp, tile_rows,
+                               gap_lo, gap_hi);
 }
 
 // Variant 70: 16 halo columns per side and 96 written columns, so every tile's loads
@@ -35,7 +35,7 @@ void vk_launch_ps10_aligned(VK_STENCIL_LAUNCH_ARGS) {
     (void)f0; (void)k;
     const double pass_bytes = 16.0 * (double)(in_hi - in_lo) * (double)ny * (double)nf;
     if (pass_bytes <= 192.0 * 1024 * 1024)
-        vk_ps::launch<10, 4, 2, 2, 16>(st, src, dst, nf, fs, ny, out_lo, out_hi, in_lo, in_hi, top, bot, coef, mm, cp);
+        vk_ps::launch<10, 4, 2, 2, 16>(st, src, dst, nf, fs, ny, out_lo, out_hi, in_lo, in_hi, top, bot, coef, mm, cp, tile_rows);
     else
-        vk_ps::launch<10, 4, 2, 0, 16>(st, src, dst, nf, fs, ny, out_lo, out_hi, in_lo, in_hi, top, bot, coef, mm, cp);
+        vk_ps::launch<10, 4, 2, 0, 16>(st, src, dst, nf, fs, ny, out_lo, out_hi, in_lo, in_hi, top, bot, coef, mm, cp, tile_rows);
 }

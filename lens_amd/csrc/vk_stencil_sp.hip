@@ -11,10 +11,8 @@
 // 48-51 (an LDS ring guarded by counters instead of the barrier).
 #include "vk_stencil_sp.h"
 
-bool vk_launch_sp(int variant, VK_STENCIL_LAUNCH_ARGS) {
-    (void)f0;
-    if (variant != 40 || k != 10 || (cp && cp->mode)) return false;
-    const int rows = g_stencil_rows > 0 ? g_stencil_rows : 0;   // 0: whole rounds of workgroups (vk_sp::round_rows)
+void vk_launch_sp(VK_STENCIL_LAUNCH_ARGS) {
+    (void)f0; (void)k; (void)cp;   // planned only for k = 10 passes that carry no coupling (vk_pass_plan.h)
+    const int rows = tile_rows > 0 ? tile_rows : 0;   // 0: whole rounds of workgroups (vk_sp::round_rows)
     vk_sp::launch<10, 4, 2, 5>(st, src, dst, nf, fs, ny, out_lo, out_hi, in_lo, in_hi, top, bot, coef, mm, rows);
-    return true;
 }

@@ -244,32 +244,19 @@ class Lattice:
 
     def coupled_plan_ok(self, timestep: float) -> bool:
         """Whether :meth:`diffuse_coupled` can run this step: a whole plane (no
-        row band, at most 8 planes) planned as two or more fused passes and no
-        single-substep pass -- vk_diffuse's planner, restated (10-deep passes in
-        the tolerance mode's depth-10 setting, else odd depths); the library makes
-        the same decision and launches nothing otherwise."""
+        row band, at most 8 planes) that the library plans as two or more fused
+        passes and no single-substep pass (vk_diffuse_plan's coupled plan; the
+        call itself makes the same decision and launches nothing otherwise)."""
         if not whole_plane(self) or len(self.molecules) > 8:
             return False
         n_sub = n_substeps(timestep, self.diffusion_dt)
-        depth = native._lib.vk_set_stencil_depth(0)
-        if depth == 10 and native._lib.vk_set_stencil_mode(-1) == 1 and n_sub % 10 == 0 and n_sub >= 20:
-            return True
-        depth = min(9 if depth == 10 else depth | 1, 15)
-        passes = (n_sub + depth - 1) // depth
-        if (passes & 1) != (n_sub & 1):
-            passes += 1
-        ks, j, left = [], 0, passes
-        while j < n_sub:
-            rem = n_sub - j
-            k = (rem + left - 1) // left
-            k += 1 - (k & 1)
-            k = min(k, depth)
-            while k > 1 and rem - k < left - 1:
-                k -= 2
-            ks.append(k)
-            j += k
-            left -= 1
-        return len(ks) >= 2 and min(ks) >= 2
+        n_passes = ctypes.c_int32(0)
+        rc = native._lib.vk_diffuse_plan(0, self.rows_local, 0, self.rows_local, 1, 1, 0, n_sub, n_sub,
+                                         native.VK_PART_ALL, 0, native.VK_PLAN_COUPLED, None, 0,
+                                         ctypes.byref(n_passes))
+        if rc != native.VK_ERR_LIMIT:
+            native.check(rc, 'vk_diffuse_plan')
+        return rc == native.VK_OK
 
     def diffuse_coupled(self, timestep: float, bin_lin, n_agents: int, seg, gather_rows, conc, count_rows,
                         counts, allreduce: Optional[Callable] = None, events=None):

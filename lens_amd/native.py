@@ -27,7 +27,7 @@ VK_AGENT_MAX_STEPS, VK_AGENT_H_UNDERFLOW, VK_AGENT_NONFINITE = 1, 2, 4
 EXPORTS = (
     'vk_abi_version', 'vk_last_error', 'vk_table_create', 'vk_table_destroy', 'vk_table_specialize',
     'vk_rate_fluxes', 'vk_step_euler', 'vk_step_dopri5', 'vk_step_dopri5_multi', 'vk_step_dopri5_gather', 'vk_field_uniform',
-    'vk_diffuse', 'vk_diffuse_part', 'vk_diffuse_delta', 'vk_diffuse_coupled', 'vk_set_stencil_depth', 'vk_set_stencil_kernel', 'vk_set_stencil_mode',
+    'vk_diffuse', 'vk_diffuse_part', 'vk_diffuse_delta', 'vk_diffuse_coupled', 'vk_diffuse_plan', 'vk_set_stencil_depth', 'vk_set_stencil_kernel', 'vk_set_stencil_mode',
     'vk_timestamp', 'vk_wall_clock_khz', 'vk_copy_stream', 'vk_gather', 'vk_exchange_sorted',
     'vk_exchange_atomic', 'vk_bin_sites', 'vk_cell_step', 'vk_divide_scratch_bytes', 'vk_divide_plan',
     'vk_divide_gather', 'vk_divide_lineage', 'vk_divide_locations', 'vk_kremling_step',
@@ -59,6 +59,7 @@ VK_RNG_STREAM, VK_RNG_PHILOX = 0, 1
 VK_DIVIDE_SET, VK_DIVIDE_SPLIT, VK_DIVIDE_ZERO = 0, 1, 2
 VK_UNIFORM_BLOCKS = 512
 VK_PART_ALL, VK_PART_INTERIOR, VK_PART_EDGES = 0, 1, 2
+VK_PLAN_COUPLED, VK_PLAN_COUPLED_AGENTS = 1, 2        # vk_diffuse_plan's coupled argument
 
 
 class NativeError(RuntimeError):
@@ -141,6 +142,12 @@ class VkSsaNet(ctypes.Structure):
                            'stoich_delta', 'rates', 'inv')]
 
 
+class VkPass(ctypes.Structure):
+    """One pass of a diffusion call's plan (vk_diffuse_plan)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ('k', 'src', 'dst', 'f0', 'lo', 'hi', 'in_lo', 'in_hi', 'gap_lo',
+                                              'gap_hi', 'kernel', 'couple', 'copy_back')]
+
+
 _SIGS = {
     'vk_abi_version': ([], ctypes.c_int),
     'vk_last_error': ([], ctypes.c_char_p),
@@ -164,6 +171,7 @@ _SIGS = {
                           _i32, _i32, _i32, _f64, _vp, _vp], ctypes.c_int),
     'vk_diffuse_coupled': ([_vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _f64, _vp, _vp, _vp, _i32, _i64,
                             _i32p, _vp, _i64, _i32p, _vp, _i64, _f64, _vp], ctypes.c_int),
+    'vk_diffuse_plan': ([_i32] * 12 + [ctypes.POINTER(VkPass), _i32, _i32p], ctypes.c_int),
     'vk_set_stencil_depth': ([_i32], ctypes.c_int),
     'vk_set_stencil_kernel': ([_i32, _i32], ctypes.c_int),
     'vk_set_stencil_mode': ([_i32], ctypes.c_int),

@@ -102,10 +102,15 @@ CASES = {
     'exact_d5_plain_stores': (33, 260, 2500, 90, 'exact', 5, 2, 12),
     'exact_d10_setting': (40, 300, 3000, 0, 'exact', 10, 20, 0),
 }
+# dt = 1.0 is ten 10-deep passes; these cases also take steps of 3, 5 and 2 passes
+# (30, 50, 20 substeps): an odd count of 10-deep passes is where the coupled step's
+# scratch buffers follow vk_diffuse's assignment rather than a rotation of their own
+SHORT_STEPS = {'d10_ragged': (0.3, 0.5, 0.2), 'exact_d10_setting': (0.3, 0.5, 0.2)}
 
 
 @pytest.mark.parametrize('case', sorted(CASES))
 def test_coupled_passes_equal_separate_launches(dev, case):
+    from lens_amd.lattice import n_substeps
     nx, ny, n, crowd, mode, depth, kernel, rows = CASES[case]
     with _stencil(mode, depth, kernel, rows):
         a, b = _pair(dev, nx, ny, n, crowd)
@@ -119,6 +124,13 @@ def test_coupled_passes_equal_separate_launches(dev, case):
         # the acetate plane was uniform (zero) before the first exchange: it must
         # have received the exchange without being diffused in that step
         assert float(a[1].owned('ac_e').abs().max()) > 0
+        for dt in SHORT_STEPS.get(case, ()):
+            assert n_substeps(dt, a[1].diffusion_dt) == round(dt * 100) and a[1].coupled_plan_ok(dt)
+            a[0].step(dt)
+            b[0].step(dt)
+            assert a[0].last_step_coupled and not b[0].last_step_coupled
+            torch.cuda.synchronize()
+            _same(a, b, (case, dt))
 
 
 def test_coupled_dopri5_graph_replay_equals_separate_launches(dev):
