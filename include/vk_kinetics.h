@@ -313,6 +313,35 @@ int vk_diffuse_plan(int32_t row_lo, int32_t row_hi, int32_t lo_min, int32_t hi_m
                     int32_t interior_passes, int32_t coupled, vk_pass *out, int32_t capacity,
                     int32_t *n_passes);
 
+/* vk_diffuse_plan with the lanes of a banded plan (vk_set_stencil_bands): beside
+ * each pass, lane[i] = the stream it is launched on (0 = the caller's, 1 = the
+ * library's second stream) and after[i] = the index of the pass on the other
+ * lane that must have finished before it starts, or -1; passes of one lane run
+ * in list order.  The caller's stream waits for lane 1 at the end of the call.
+ * An unbanded plan is all lane 0, after -1.  lane / after: capacity entries
+ * each, nullable.  Not a reference interface (as vk_diffuse_plan).          */
+int vk_diffuse_plan_lanes(int32_t row_lo, int32_t row_hi, int32_t lo_min, int32_t hi_max, int32_t edge_top,
+                          int32_t edge_bot, int32_t sub_begin, int32_t sub_count, int32_t n_sub,
+                          int32_t part, int32_t interior_passes, int32_t coupled, vk_pass *out,
+                          int32_t *lane, int32_t *after, int32_t capacity, int32_t *n_passes);
+
+/* Row bands of a whole-plane step on two streams.  A tolerance-mode step of P
+ * 10-deep pair-sum passes over the whole plane (vk_diffuse with rows [0, N),
+ * both edges reflected, every substep; not vk_diffuse_coupled) can run each
+ * pass as two launches: a top band, rows [0, m_p), on the caller's stream and
+ * a bottom band, rows [m_p, N), on a stream the library owns, m_p = top_rows -
+ * 10 p.  The top bands then never wait for the bottom bands, and the end of
+ * one launch overlaps the start of the next; results are bit-identical.
+ * bands: 1 = off, 2 = forced with m_0 = top_rows (a step whose last top band
+ * would have fewer than 10 rows, or whose first bottom band none, runs
+ * unbanded), 0 = the automatic rule (the default: bands only the shape measured
+ * faster banded, DESIGN.md §10 -- a 4096-row plane stepping ten passes of variant
+ * 70, with m_0 = 1638).  Returns the previous bands; other values only query
+ * (top_rows has no query).  The second stream and its events are created by
+ * the first banded call whose stream is not capturing; a captured call before
+ * that runs unbanded.  Tuning only.                                         */
+int vk_set_stencil_bands(int32_t bands, int32_t top_rows);
+
 /* Maximum substeps fused per HBM pass by vk_diffuse (temporal blocking; odd,
  * 1..15; 1 = one launch per substep; or 10, the default: a block of a multiple
  * of 10 substeps as 10-deep passes -- in the tolerance mode over three buffers

@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <mutex>
 #include <utility>
 #include <vector>
 
@@ -191,8 +192,60 @@ __global__ __launch_bounds__(256) void k_copy_rows(const double *__restrict__ sr
 // (vk_pass_plan.h), launch each pass of the plan
 // ---------------------------------------------------------------------------
 
+// Row bands of a whole-plane step on two streams (vk_plan::plan_lanes): 0 = the
+// automatic rule, 1 = off, 2 = forced, the top band of the first pass top_rows rows
+static int g_stencil_bands = 0;
+static int g_stencil_top_rows = 0;
+
+extern "C" int vk_set_stencil_bands(int32_t bands, int32_t top_rows) {
+    const int prev = g_stencil_bands;
+    if (bands == 0 || bands == 1 || (bands == 2 && top_rows > 0)) {
+        g_stencil_bands = bands;
+        g_stencil_top_rows = bands == 2 ? top_rows : 0;
+    }
+    return prev;
+}
+
 static vk_plan::Settings stencil_settings() {
-    return {g_stencil_mode, g_stencil_depth, g_stencil_kernel, g_stencil_rows};
+    return {g_stencil_mode, g_stencil_depth, g_stencil_kernel, g_stencil_rows, g_stencil_bands, g_stencil_top_rows};
+}
+
+// Lane 1 of a banded plan: one non-blocking stream per device, owned by the library,
+// and the events that order the two lanes (timing disabled; a pass's wait takes the
+// event's state when it is enqueued, so the next call records the same events again).
+// Made by the first banded call that finds the caller's stream not capturing: nothing
+// is created under capture, where a call without them runs the unbanded plan.  A
+// device's banded calls share them, so (like the settings) they are for one host
+// thread at a time.
+constexpr int BAND_EVENTS = 66;    // the fork, the join, and one per pass of the longest plan (64 passes)
+struct BandLanes {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[BAND_EVENTS] = {};
+};
+static std::mutex g_band_mutex;
+static std::vector<BandLanes *> g_band_lanes;   // by device
+
+static BandLanes *band_lanes(hipStream_t caller) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0) return nullptr;
+    std::lock_guard<std::mutex> lock(g_band_mutex);
+    if ((size_t)dev >= g_band_lanes.size()) g_band_lanes.resize(dev + 1, nullptr);
+    if (g_band_lanes[dev]) return g_band_lanes[dev];
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(caller, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return nullptr;
+    BandLanes *l = new BandLanes;
+    bool ok = hipStreamCreateWithFlags(&l->stream, hipStreamNonBlocking) == hipSuccess;
+    for (int i = 0; ok && i < BAND_EVENTS; ++i) ok = hipEventCreateWithFlags(&l->ev[i], hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+        for (hipEvent_t e : l->ev)
+            if (e) (void)hipEventDestroy(e);
+        if (l->stream) (void)hipStreamDestroy(l->stream);
+        delete l;
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    g_band_lanes[dev] = l;
+    return l;
 }
 
 // What a call's passes share: the three buffers (indexed by VK_BUF_*), the planes,
@@ -237,17 +290,54 @@ static void launch_pass(const vk_pass &p, const PassArgs &a) {
 static int run_plan(const char *what, const vk_plan::Call &c, double *field, double *work0, double *work1, int32_t n_fields,
                     int64_t field_stride, int32_t ny, double coeff_dt, const double *uniform, const VkPsCouple *cp,
                     vk_stream_t stream) {
-    const vk_plan::Settings st = stencil_settings();
+    vk_plan::Settings st = stencil_settings();
     std::vector<vk_pass> passes;
+    std::vector<int32_t> lane, after;
     const char *why = "";
-    int rc = vk_plan::plan(st, c, passes, &why);
+    int rc = vk_plan::plan_lanes(st, c, passes, lane, after, &why);
     if (rc) {
         vk::set_error("%s: %s", what, why);
         return rc;
     }
     if (n_fields == 0) return VK_OK;
-    const PassArgs a = {{field, work0, work1}, n_fields, field_stride, ny, c.edge_top ? c.lo_min : -1,
-                        c.edge_bot ? c.hi_max - 1 : 0x7fffffff, st.rows, coeff_dt, uniform, cp, (hipStream_t)stream};
+    // A banded plan: lane 0 is the caller's stream, lane 1 the library's.  Lane 1 starts
+    // after what the caller's stream holds (the fork); a pass with an `after` waits for
+    // the event recorded behind that pass; the caller's stream ends waiting for lane 1's
+    // last pass (the join), so whatever follows the call sees the whole step.
+    const bool banded = std::find(lane.begin(), lane.end(), 1) != lane.end();
+    BandLanes *bl = banded ? band_lanes((hipStream_t)stream) : nullptr;
+    // the event of each pass that another waits for
+    std::vector<int> slot(passes.size(), -1);
+    int slots = 0;
+    for (int32_t i : after)
+        if (i >= 0 && slot[i] < 0) slot[i] = slots++;
+    if (banded && (!bl || slots + 2 > BAND_EVENTS)) {   // (no lanes yet, under capture)
+        st.bands = 1;
+        bl = nullptr;
+        if ((rc = vk_plan::plan_lanes(st, c, passes, lane, after, &why))) return rc;
+    }
+    PassArgs a = {{field, work0, work1}, n_fields, field_stride, ny, c.edge_top ? c.lo_min : -1,
+                  c.edge_bot ? c.hi_max - 1 : 0x7fffffff, st.rows, coeff_dt, uniform, cp, (hipStream_t)stream};
+    if (bl) {
+        hipStream_t lanes[2] = {(hipStream_t)stream, bl->stream};
+        hipEvent_t fork = bl->ev[BAND_EVENTS - 2], join = bl->ev[BAND_EVENTS - 1];
+        if ((rc = vk::hip_check(hipEventRecord(fork, lanes[0]), what))) return rc;
+        if ((rc = vk::hip_check(hipStreamWaitEvent(lanes[1], fork, 0), what))) return rc;
+        // Once lane 1 has joined the caller's work (and, under capture, its capture) the
+        // join below must be reached: a failed launch is reported after it.
+        int failed = VK_OK;
+        for (size_t i = 0; i < passes.size() && !failed; ++i) {
+            a.stream = lanes[lane[i]];
+            if (after[i] >= 0) failed = vk::hip_check(hipStreamWaitEvent(a.stream, bl->ev[slot[after[i]]], 0), what);
+            if (failed) break;
+            launch_pass(passes[i], a);
+            failed = vk::launch_check(what);
+            if (!failed && slot[i] >= 0) failed = vk::hip_check(hipEventRecord(bl->ev[slot[i]], a.stream), what);
+        }
+        rc = vk::hip_check(hipEventRecord(join, lanes[1]), what);
+        if (!rc) rc = vk::hip_check(hipStreamWaitEvent(lanes[0], join, 0), what);
+        return failed ? failed : rc;
+    }
     for (const vk_pass &p : passes) {
         launch_pass(p, a);
         if ((rc = vk::launch_check(what))) return rc;
@@ -293,10 +383,10 @@ extern "C" int vk_diffuse(double *field, double *work0, double *work1, int32_t n
                            edge_bot, sub_begin, sub_count, n_sub, coeff_dt, uniform, VK_PART_ALL, 0, stream);
 }
 
-extern "C" int vk_diffuse_plan(int32_t row_lo, int32_t row_hi, int32_t lo_min, int32_t hi_max, int32_t edge_top,
-                               int32_t edge_bot, int32_t sub_begin, int32_t sub_count, int32_t n_sub, int32_t part,
-                               int32_t interior_passes, int32_t coupled, vk_pass *out, int32_t capacity,
-                               int32_t *n_passes) {
+extern "C" int vk_diffuse_plan_lanes(int32_t row_lo, int32_t row_hi, int32_t lo_min, int32_t hi_max, int32_t edge_top,
+                                     int32_t edge_bot, int32_t sub_begin, int32_t sub_count, int32_t n_sub,
+                                     int32_t part, int32_t interior_passes, int32_t coupled, vk_pass *out,
+                                     int32_t *lane, int32_t *after, int32_t capacity, int32_t *n_passes) {
     const vk_plan::Call c = {row_lo,    row_hi,    lo_min, hi_max, edge_top,        edge_bot,
                              sub_begin, sub_count, n_sub,  part,   interior_passes, coupled};
     const bool whole_step = row_lo == 0 && lo_min == 0 && row_hi == hi_max && sub_begin == 0 && sub_count == n_sub &&
@@ -307,12 +397,24 @@ extern "C" int vk_diffuse_plan(int32_t row_lo, int32_t row_hi, int32_t lo_min, i
         return VK_ERR_ARG;
     }
     std::vector<vk_pass> passes;
+    std::vector<int32_t> lanes, afters;
     const char *why = "";
-    const int rc = vk_plan::plan(stencil_settings(), c, passes, &why);
+    const int rc = vk_plan::plan_lanes(stencil_settings(), c, passes, lanes, afters, &why);
     if (rc) vk::set_error("vk_diffuse_plan: %s", why);
     *n_passes = (int32_t)passes.size();
-    std::copy_n(passes.begin(), std::min<size_t>(passes.size(), (size_t)capacity), out);
+    const size_t n = std::min<size_t>(passes.size(), (size_t)capacity);
+    std::copy_n(passes.begin(), n, out);
+    if (lane) std::copy_n(lanes.begin(), n, lane);
+    if (after) std::copy_n(afters.begin(), n, after);
     return rc;
+}
+
+extern "C" int vk_diffuse_plan(int32_t row_lo, int32_t row_hi, int32_t lo_min, int32_t hi_max, int32_t edge_top,
+                               int32_t edge_bot, int32_t sub_begin, int32_t sub_count, int32_t n_sub, int32_t part,
+                               int32_t interior_passes, int32_t coupled, vk_pass *out, int32_t capacity,
+                               int32_t *n_passes) {
+    return vk_diffuse_plan_lanes(row_lo, row_hi, lo_min, hi_max, edge_top, edge_bot, sub_begin, sub_count, n_sub, part,
+                                 interior_passes, coupled, out, nullptr, nullptr, capacity, n_passes);
 }
 
 // A whole-plane step's passes with the agent coupling inside them: the first

@@ -3,7 +3,7 @@
 // the one it writes, its rows and its kernel family.  Pure host code -- no HIP header,
 // no global: vk_lattice.hip fills the settings from vk_set_stencil_*, plans, and turns
 // each pass into its launch; vk_diffuse_plan hands the same list to callers and to the
-// CPU test (tests/test_pass_plan_host.py).
+// CPU tests (tests/test_pass_plan_host.py, tests/test_band_plan_host.py).
 #pragma once
 
 #include <stdint.h>
@@ -20,6 +20,8 @@ struct Settings {
     int depth;    // vk_set_stencil_depth: odd 1..15, or 10
     int kernel;   // vk_set_stencil_kernel's variant
     int rows;     // ... and its rows per wave tile (0 = auto); the launchers' tile_rows, no part of the plan
+    int bands;    // vk_set_stencil_bands: 0 = automatic rule, 1 = off, 2 = forced (plan_lanes only)
+    int top_rows; // ... and the forced top band's rows in the first pass, m_0
 };
 
 // A call's geometry as vk_diffuse_part takes it; coupled: VK_PLAN_* (vk_diffuse_coupled's
@@ -188,6 +190,60 @@ inline int plan(const Settings &s, const Call &c, std::vector<vk_pass> &out, con
         j += k;
     }
     return VK_OK;
+}
+
+// The top band's rows in the first pass, m_0, with which the automatic rule
+// (Settings::bands == 0) runs a plan banded, or 0.  Only the shape measured faster
+// banded than whole: the 4096-row plane stepping ten aligned 10-deep passes (variant 70,
+// the C4 step: 1.170-1.178 against 1.245-1.260 ms per step with the top two fifths,
+// m_0 = 1638; 1600-1800 and 2418-2500 rows within 0.02 ms of that, halves in lockstep
+// and a top band of 0.35 or less, whose launches fall under the cached-store size, no
+// better than whole; DESIGN.md §10, profiles/bands/).
+inline int auto_top_rows(const Call &c, const std::vector<vk_pass> &passes) {
+    if (c.row_hi - c.row_lo != 4096 || passes.size() != 10) return 0;
+    for (const vk_pass &p : passes)
+        if (p.kernel != VK_PASS_PS10_ALIGNED) return 0;
+    return 2 * 4096 / 5;
+}
+
+// The call's passes as plan() lists them, or, for a whole-plane step of P 10-deep
+// pair-sum passes, each pass as two launches on two lanes (streams): a top band T_p =
+// rows [0, m_p) on lane 0 and a bottom band B_p = [m_p, N) on lane 1, m_p = m_0 - 10 p.
+// The boundary climbs by the pass depth, so T_p+1 reads only rows T_p wrote: lane 0 is
+// a chain that never waits for lane 1, and B_p+1 (which reads from row m_p - 20) needs
+// B_p, its lane's order, and T_p, its `after`.  A later T writes only rows above
+// m_p - 10, which a lagging B_p neither reads nor writes, in any buffer.  The tails of
+// one lane's launches then run beside the other lane's next launch.  lane[i] and
+// after[i] (the index of the pass on the other lane that must have finished, or -1) run
+// parallel to `out`; an unbanded plan is all lane 0, after -1.  Unbanded when the
+// setting says so, for any other call (a part, a row band, a coupled step, other
+// kernels), when T_P-1 would have fewer rows than one pass depth or B_0 none.
+inline int plan_lanes(const Settings &s, const Call &c, std::vector<vk_pass> &out, std::vector<int32_t> &lane,
+                      std::vector<int32_t> &after, const char **why) {
+    const int rc = plan(s, c, out, why);
+    lane.assign(out.size(), 0);
+    after.assign(out.size(), -1);
+    if (rc != VK_OK || s.bands == 1 || out.empty()) return rc;
+    const bool whole_step = c.part == VK_PART_ALL && c.edge_top && c.edge_bot && c.row_lo == c.lo_min &&
+                            c.row_hi == c.hi_max && c.sub_begin == 0 && c.sub_count == c.n_sub && !c.coupled;
+    if (!whole_step) return rc;
+    for (const vk_pass &p : out)
+        if (p.k != 10 || (p.kernel != VK_PASS_PS10 && p.kernel != VK_PASS_PS10_ALIGNED) || p.copy_back) return rc;
+    const int P = (int)out.size(), N = c.row_hi - c.row_lo;
+    const int m0 = s.bands == 2 ? s.top_rows : auto_top_rows(c, out);
+    if (m0 - 10 * (P - 1) < 10 || m0 >= N) return rc;
+    std::vector<vk_pass> banded;
+    lane.clear(), after.clear();
+    for (int p = 0; p < P; ++p) {
+        const int m = c.row_lo + m0 - 10 * p;
+        vk_pass t = out[p], b = out[p];
+        t.hi = m, t.in_hi = std::min(c.hi_max, m + 10);
+        b.lo = m, b.in_lo = std::max(c.lo_min, m - 10);
+        banded.push_back(t), lane.push_back(0), after.push_back(-1);
+        banded.push_back(b), lane.push_back(1), after.push_back(p ? 2 * (p - 1) : -1);   // B_p after T_p-1
+    }
+    out.swap(banded);
+    return rc;
 }
 
 }  // namespace vk_plan

@@ -79,6 +79,20 @@ def stencil_mode(mode=None) -> str:
     return names[native._lib.vk_set_stencil_mode(code)]
 
 
+def stencil_bands(bands: int = -1, top_rows: int = 0) -> int:
+    """Set / query (-1) the row bands of a whole-plane step of 10-deep pair-sum passes;
+    returns the previous setting.  1 = off; 2 = every pass as a top band of ``top_rows``
+    rows less 10 per pass on the caller's stream and the rest of the plane on a second
+    stream (vk_set_stencil_bands; bit-identical results); 0 = the automatic rule (the
+    default), which bands only shapes measured faster banded."""
+    native.load()
+    if int(bands) not in (-1, 0, 1, 2):
+        raise ValueError('stencil bands must be 0 (auto), 1 (off) or 2 (forced), got %d' % bands)
+    if int(bands) == 2 and int(top_rows) <= 0:
+        raise ValueError('forced stencil bands need the top band\'s rows, got %d' % top_rows)
+    return native._lib.vk_set_stencil_bands(int(bands), int(top_rows))
+
+
 class Lattice:
     def __init__(self, molecules: Sequence[str], n_bins, bounds, depth: float, diffusion: float,
                  device=None, row_band=None, halo: int = 0, avogadro: float = N_A_LEGACY,
