@@ -37,7 +37,7 @@
  *   vk_cell_step / vk_divide_*, vk_kremling_step, vk_expression_step,
  *   vk_motility_step, vk_flagella_step, vk_contact_step, vk_contact_step_channels, vk_population_plan,
  *   vk_flagella_counts, vk_divide_flagella, vk_ssa_step, vk_ssa_propensities, vk_divide_counts,
- *   vk_ssa_flagella_target
+ *   vk_ssa_flagella_target, vk_colony_metrics
  *       are introduced by the comment blocks above their declarations.
  *
  * Conventions
@@ -1017,6 +1017,105 @@ int vk_contact_step_channels(const vk_contact_params *p, int64_t n_agents, int64
                              int32_t ny, double bound_x, double bound_y, int32_t *bin_lin,
                              int32_t *bin_ix, void *scratch, int64_t scratch_bytes,
                              const vk_contact_channels *ch, int32_t *outflow, vk_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Colony metrics: connected colonies, mass, area, axes
+ *
+ *   vk_colony_metrics
+ *       stands where the reference wires its ColonyShapeDeriver into the
+ *       lattice (vivarium/compartments/lattice.py:61-64,
+ *       vivarium/processes/derive_colony_shape.py:97-217) and emits
+ *       colony_global.  The definition is THIS ENGINE'S OWN, not alphashape's:
+ *       no polygon is built, there is no circumference, and the area is the
+ *       sum of the capsules' own areas.  The colony count and the colony
+ *       masses agree with the reference on its own seven test scenarios
+ *       (cells as unit circles, link_gap 0.25).
+ *
+ * Agents are vk_contact_step's capsules (r = w / 2, h = max(L - w, 0) / 2).
+ * Link: agents i != j are linked when (2 r + link_gap) - d_ij >= 0, d_ij the
+ * distance of the closest points of the two spines by the contact kernel's own
+ * arithmetic (its closest-point solve and clamps, the den > 1e-12 parallel
+ * branch, d = 0 for coincident spines).  An agent whose x or y is not finite
+ * links to nobody and gets colony = -1 whatever min_cells is.
+ * Colony: a connected component of the link graph with >= min_cells members;
+ * agents of smaller components get colony = -1.  Colonies are numbered
+ * 0 .. C - 1 in the order of their first member in ascending (grid cell, key)
+ * order; colony_key[c] is the smallest key among the members.  Nothing depends
+ * on the storage order or the launch geometry.
+ * Per colony c, over its members in ascending (grid cell, key) order:
+ *   cells[c]                 the member count
+ *   VK_COLONY_MASS           sum of mass (p->mass each when mass is NULL)
+ *   VK_COLONY_CELL_AREA      sum of w max(L - w, 0) + pi w^2 / 4 (overlaps of
+ *                            two capsules are counted twice)
+ *   VK_COLONY_CX, _CY        the mean of the centres
+ *   VK_COLONY_SXX, _SYY, _SXY   the second moments of the centres about it
+ *   VK_COLONY_ANGLE          phi = 0.5 atan2(2 sxy, sxx - syy); isotropic: 0
+ *   VK_COLONY_MAJOR, _MINOR  the larger and the smaller of the extents along
+ *                            e1 = (cos phi, sin phi) and across it; along e:
+ *                            max(p.e + h |u.e| + r) - min(p.e - h |u.e| - r)
+ *                            over the members, p taken about the centroid
+ * Sum order (also of min and max).  A run of members is combined by one
+ * workgroup of 256 threads: thread t combines members t, t + 256, t + 512, ...
+ * of the run in that order starting from the identity; each wave of 64
+ * combines its lanes by the butterfly p = p op shfl_xor(p, o), o = 32, 16, 8,
+ * 4, 2, 1; the four waves are combined as ((w0 op w1) op w2) op w3.  A colony
+ * of at most 512 members is one run; a larger one is 64 runs of
+ * S = 256 ceil(size / 16384) consecutive members each (the last may be short
+ * or empty: the identity), combined in order as ((P0 op P1) op P2) ... op P63.
+ * A function of the member sequence alone.  No floating-point atomics.
+ * lens_amd/csrc/vk_colonies.hip states every formula.
+ * ------------------------------------------------------------------------- */
+
+enum vk_colony_row {
+    VK_COLONY_MASS = 0,
+    VK_COLONY_CELL_AREA = 1,
+    VK_COLONY_CX = 2,
+    VK_COLONY_CY = 3,
+    VK_COLONY_SXX = 4,
+    VK_COLONY_SYY = 5,
+    VK_COLONY_SXY = 6,
+    VK_COLONY_ANGLE = 7,
+    VK_COLONY_MAJOR = 8,
+    VK_COLONY_MINOR = 9,
+    VK_COLONY_ROWS = 10
+};
+
+enum vk_colonies_flag {
+    VK_COLONIES_TOO_LONG = 1,   /* an agent is longer than max_length (or than a grid cell's edge) */
+    VK_COLONIES_GAVE_UP = 2     /* a union ran out of retries: the labels are not to be used      */
+};
+
+typedef struct vk_colonies_params {
+    int32_t gx, gy;                      /* neighbour grid: max(1, floor(bound / (max_length + link_gap))) per axis */
+    int32_t min_cells;                   /* >= 1: the members a component needs to be a colony */
+    int32_t reserved;
+    double max_length;                   /* um: no agent is longer (bit 0 of flags otherwise) */
+    double width;                        /* um, every agent's                          */
+    double length;                       /* um, every agent's when length is NULL      */
+    double link_gap;                     /* um, >= 0: capsules closer than this are linked */
+    double mass;                         /* every agent's mass when mass is NULL       */
+} vk_colonies_params;
+
+/* Scratch of vk_colony_metrics for n agents on a grid of n_grid_cells = gx * gy. */
+int64_t vk_colonies_scratch_bytes(int64_t n_agents, int64_t n_grid_cells);
+
+/* Colonies of agents [0, n): location ([2][ld]), angle ([ld]), length ([ld],
+ * NULL: p->length), mass ([ld], NULL: p->mass) and key ([ld] int64, NULL: the
+ * column index; distinct, < 2^32) are read.  Outputs: colony ([ld] int32: the
+ * colony of each agent of [0, n), or -1), n_colonies (one device int32: C),
+ * cells ([ld] int32), colony_key ([ld] int64) and metrics ([VK_COLONY_ROWS][ld]
+ * doubles; NULL: labels, cells and keys only); entries at or beyond C are not
+ * written.  flags: one int32 the caller zeroes; vk_colonies_flag bits are ORed
+ * in (the call still runs).  scratch: 256-B aligned, >=
+ * vk_colonies_scratch_bytes(n, gx * gy).  Argument errors return VK_ERR_ARG and
+ * launch nothing; n == 0 returns VK_OK with *n_colonies = 0.  No host
+ * synchronisation: the call can be captured into a graph.  No kernel waits on
+ * another workgroup and nothing is polled.                                   */
+int vk_colony_metrics(const vk_colonies_params *p, int64_t n_agents, int64_t ld, const double *location,
+                      const double *angle, const double *length, const double *mass,
+                      const int64_t *key, double bound_x, double bound_y, int32_t *colony,
+                      int32_t *n_colonies, int32_t *cells, int64_t *colony_key, double *metrics,
+                      int32_t *flags, void *scratch, int64_t scratch_bytes, vk_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Antibiotic response: membrane diffusion, death, the float exchange

@@ -47,6 +47,11 @@ the top, which take part in the step (their exchange lands) and leave at its end
 in the same plan as division (vk_population_plan), or through :meth:`Colony.remove`
 when there are no cells.  ``remove(mask)`` takes agents out of any unrouted colony.
 
+:meth:`Colony.colony_metrics` says which cells of such a colony form a connected colony
+and gives each colony's cell count, mass, area, centroid and axes (lens_amd/colonies.py,
+standing where the reference's ColonyShapeDeriver emits ``colony_global``); it is a call
+of its own and no part of the step.
+
 With a :class:`~lens_amd.response.CellResponse` (``response=``) each agent is the
 reference's antibiotic-response cell: before the kinetics launch the death
 detector and the membrane's porin diffusion are evaluated from the step-start
@@ -81,6 +86,7 @@ import torch
 
 from lens_amd import native
 from lens_amd.cells import CellModel, lineage_ids
+from lens_amd.colonies import ColonyShape, ColonyShapeModel
 from lens_amd.configs import initial_conc
 from lens_amd.expression import ExpressionEngine
 from lens_amd.kinetics import KineticsEngine
@@ -132,7 +138,7 @@ _ALL_AGENT_ARRAYS = AGENT_ARRAYS + STOCHASTIC_ARRAYS
 # Tensors sized by the capacity that are not per-agent state: Colony._capacity_scratch
 # allocates them (the first row) or drops them for their users to allocate again (the second)
 CAPACITY_SCRATCH = ('bin_lin', 'bin_ix', 'env_bins', 'outflow', '_flag_expr_update', 'ssa_events', '_ssa_status',
-                    '_counts_alt', 'flux_steps', 'counts_steps', 'nsteps_steps')
+                    '_counts_alt', 'flux_steps', 'counts_steps', 'nsteps_steps', '_colony_shape')
 
 
 class Colony:
@@ -144,6 +150,7 @@ class Colony:
     stochastic = _ssa = ssa = ssa_key = None     # Colony(stochastic=...)
     _x_stream = _p_stream = None                 # capture(overlap=True)
     _counts_alt = flux_steps = counts_steps = nsteps_steps = None    # capture(overlap=True), step_many
+    _colony_shape = None                         # colony_metrics
 
     def __init__(self, config, n_agents: int, *, capacity: Optional[int] = None, device=None,
                  integrator: str = 'dopri5', rtol: float = 1e-8, atol: float = 1e-12,
@@ -271,6 +278,7 @@ class Colony:
         self.conc = torch.from_numpy(conc0).to(dev).contiguous()
         self.m2c = torch.full((ld,), mmol_to_counts_from_mass(mass_fg, avogadro=avogadro),
                               dtype=torch.float64, device=dev)
+        self.mass_fg = float(mass_fg)        # every agent's mass when there are no cells (colony_metrics)
         self.flux = z(t.n_reactions, ld)
         self.counts = z(t.n_ext, ld, dtype=torch.int64)
         self.status = z(ld, dtype=torch.int32)
@@ -406,8 +414,9 @@ class Colony:
             # the events each agent fired in the last step; the status bits are sticky and
             # checked before the capacity changes (_regather), so nothing is lost here
             self.ssa_events, self._ssa_status = i32(), i32()
-        # sized by ld too, allocated by their users (capture(overlap=True), step_many)
+        # sized by ld too, allocated by their users (capture(overlap=True), step_many, colony_metrics)
         self._counts_alt = self.flux_steps = self.counts_steps = self.nsteps_steps = None
+        self._colony_shape = None
         self._layout += 1
 
     # -- maps between SoA rows and field planes ---------------------------------
@@ -914,6 +923,32 @@ class Colony:
         if self.exchange_mode == 'sorted' and (self.map_exch_count.numel() or self.response is not None):
             lat = self.lattice
             self._occ_dev.sort(self.bin_lin, self.n, lat.rows_local * lat.ny, key)
+
+    def colony_metrics(self, link_gap: float = 0.5, min_cells: int = 3):
+        """Which cells form a colony, and each colony's cell count, mass, cell area,
+        centroid, angle and axes (lens_amd/colonies.py: this engine's own definition,
+        standing where the reference's ColonyShapeDeriver emits ``colony_global``).
+        For colonies with ``mechanics=``: width and max_length are the ContactModel's,
+        angle and length come from where the contact launch takes them, mass from the
+        cells' mass row (``cells=``) or the colony's ``mass_fg``, the key is
+        ``agent_order``.  Returns a :class:`~lens_amd.colonies.ColonyMetrics` (a host
+        read).  The buffers are made on first use and dropped when the capacity
+        changes; a colony that never calls this launches nothing for it."""
+        if self.mechanics is None:
+            raise ValueError('colony_metrics needs a colony with mechanics= (the capsules\' width and max_length)')
+        shape = self._colony_shape
+        if shape is None or (shape.model.link_gap, shape.model.min_cells) != (float(link_gap), int(min_cells)):
+            model = ColonyShapeModel(link_gap=link_gap, min_cells=min_cells, max_length=self.mechanics.max_length,
+                                     width=self.mechanics.width)
+            shape = self._colony_shape = ColonyShape(model, self.lattice.bounds, self.ld, self.device,
+                                                     length=self.mechanics.length, mass=self.mass_fg)
+        if self.cells is not None:
+            angle, length = self.cell[native.VK_CELL_ANGLE], self.cell[native.VK_CELL_LENGTH]
+            mass = self.cell[native.VK_CELL_MASS]
+        else:
+            angle, length, mass = self.mech_angle, None, None
+        shape.launch(self.n, self.location, angle, length=length, mass=mass, key=self.agent_order)
+        return shape.result()
 
     # -- the antibiotic response (lens_amd/response.py) ----------------------------
     def _response_begin(self, dt):

@@ -32,7 +32,9 @@
 //   k_contact_relax   one thread per sorted slot; cells (cx', cy-1 .. cy+1) are adjacent in
 //                     the sorted array, so an agent reads three contiguous runs.  Writes the
 //                     agent's own column; `packed` is the snapshot, so the write is in place.
-// The last iteration also writes bin_lin / bin_ix with vk_bin_sites' arithmetic.
+// The last iteration also writes bin_lin / bin_ix with vk_bin_sites' arithmetic.  The cells and
+// pack kernels and the closest-point routine live in vk_capsule_grid.h, which the colony
+// metrics (vk_colonies.hip) include too.
 //
 // Channels (vk_contact_step_channels, the reference's mother machine: pymunk_multibody.py:
 // 218-230, multibody_physics.py:232-250): vertical lines at x = space * l, l < n_lines, from the
@@ -53,14 +55,9 @@
 #include <stdint.h>
 
 #include "vk_bin.h"
+#include "vk_capsule_grid.h"
 #include "vk_internal.h"
 #include "vk_philox.h"
-
-static inline int64_t align256(int64_t b) { return (b + 255) & ~(int64_t)255; }
-
-struct contact_slot {   // 32 B: one agent of the snapshot, in sorted order
-    double x, y, theta, L;
-};
 
 // scratch layout: cell[n] i32 | order[n] i32 | sorted_cell[n] i32 | skey[n] u32 |
 // packed[n] 32 B | dir[n] 16 B | cell_start[g] i32 | cell_end[g] i32 | the sort's scratch
@@ -73,55 +70,7 @@ extern "C" int64_t vk_contact_scratch_bytes(int64_t n, int64_t n_grid_cells) {
     return contact_fixed_bytes(n, n_grid_cells) + vk_occupancy_scratch_bytes(n) + 256;
 }
 
-// cell index along one axis: min(g - 1, floor(x / edge)); anything else (a location outside
-// [0, bound), a NaN) lands in an end cell instead of outside the tables
-__device__ __forceinline__ int contact_cell_axis(double x, double edge, int g) {
-    const double v = floor(x / edge);
-    if (!(v >= 0.0)) return 0;
-    return v < (double)g ? (int)v : g - 1;
-}
-
-__global__ __launch_bounds__(256) void k_contact_cells(int n, int64_t ld, const double *__restrict__ loc,
-                                                       const double *__restrict__ length, double length_const,
-                                                       double edge_x, double edge_y, int gx, int gy,
-                                                       int32_t *__restrict__ cell, int32_t *__restrict__ flags) {
-    const int a = blockIdx.x * blockDim.x + threadIdx.x;
-    if (a >= n) return;
-    const int cx = contact_cell_axis(loc[a], edge_x, gx);
-    const int cy = contact_cell_axis(loc[ld + a], edge_y, gy);
-    cell[a] = cx * gy + cy;
-    const double L = length ? length[a] : length_const;
-    if (L > edge_x || L > edge_y) atomicOr(flags, 1);
-}
-
-__global__ __launch_bounds__(256) void k_contact_pack(int n, int64_t ld, const double *__restrict__ loc,
-                                                      const double *__restrict__ angle,
-                                                      const double *__restrict__ length, double length_const,
-                                                      const int64_t *__restrict__ key,
-                                                      const int32_t *__restrict__ order,
-                                                      const int32_t *__restrict__ sorted_cell,
-                                                      contact_slot *__restrict__ packed, double2 *__restrict__ dir,
-                                                      uint32_t *__restrict__ skey, int32_t *__restrict__ cell_start,
-                                                      int32_t *__restrict__ cell_end) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    const int a = order[k];
-    contact_slot s;
-    s.x = loc[a];
-    s.y = loc[ld + a];
-    s.theta = angle[a];
-    s.L = length ? length[a] : length_const;
-    packed[k] = s;
-    dir[k] = make_double2(cos(s.theta), sin(s.theta));
-    skey[k] = key ? (uint32_t)key[a] : (uint32_t)a;
-    const int c = sorted_cell[k];
-    if (k == 0 || sorted_cell[k - 1] != c) cell_start[c] = k;
-    if (k == n - 1 || sorted_cell[k + 1] != c) cell_end[c] = k + 1;
-}
-
 #define CONTACT_CAND 16   // candidates a lane collects before it solves them
-
-__device__ __forceinline__ double clampd(double v, double lo, double hi) { return fmin(fmax(v, lo), hi); }
 
 // CH: the mother machine's channel walls and outflow flag (vk_contact_step_channels); the
 // instantiation without them is the kernel as it was.
@@ -149,24 +98,9 @@ __global__ __launch_bounds__(256) void k_contact_relax(
         const contact_slot o = packed[j];
         const double2 uj = dir[j];
         const double hj = fmax(o.L - p.width, 0.0) / 2.0;
-        // closest points of the two spines
-        const double rx = me.x - o.x, ry = me.y - o.y;
-        const double b = ui.x * uj.x + ui.y * uj.y;
-        const double cp = ui.x * rx + ui.y * ry;
-        const double f = uj.x * rx + uj.y * ry;
-        const double den = 1.0 - b * b;
-        double s = den > 1e-12 ? clampd((b * f - cp) / den, -hi, hi) : 0.0;
-        double t = b * s + f;
-        if (t < -hj) {
-            t = -hj;
-            s = clampd(-b * hj - cp, -hi, hi);
-        } else if (t > hj) {
-            t = hj;
-            s = clampd(b * hj - cp, -hi, hi);
-        }
-        const double vx = (me.x + s * ui.x) - (o.x + t * uj.x);
-        const double vy = (me.y + s * ui.y) - (o.y + t * uj.y);
-        const double d = sqrt(vx * vx + vy * vy);
+        // closest points of the two spines (vk_capsule_grid.h)
+        double rx, ry, s, vx, vy;
+        const double d = contact_closest(me, ui, hi, o, uj, hj, rx, ry, s, vx, vy);
         const double delta = (r + r) - d;
         if (!(delta > 0.0)) return;
         double nxn, nyn;

@@ -37,6 +37,7 @@ EXPORTS = (
     'vk_exchange_atomic_f64', 'vk_population_scratch_bytes', 'vk_population_plan', 'vk_contact_step_channels',
     'vk_flagella_step', 'vk_flagella_counts', 'vk_divide_flagella',
     'vk_ssa_step', 'vk_ssa_propensities', 'vk_divide_counts', 'vk_ssa_flagella_target',
+    'vk_colonies_scratch_bytes', 'vk_colony_metrics',
 )
 
 VK_CELL_MASS, VK_CELL_VOLUME, VK_CELL_LENGTH, VK_CELL_SURFACE_AREA, VK_CELL_PROTEIN, VK_CELL_ANGLE = range(6)
@@ -54,6 +55,10 @@ VK_SSA_MAX_SPECIES, VK_SSA_MAX_REACTIONS, VK_SSA_MAX_ORDER = 64, 32, 255
 VK_SSA_DOMAIN = 0x7373615f73746570                 # mixed into the seed of vk_ssa_step's draws
 VK_SSA_DIVIDE_DOMAIN = 0x7373615f64697669          # and of vk_divide_counts' coins
 VK_SSA_MAX_EVENTS, VK_SSA_NONFINITE, VK_SSA_OVERFLOW, VK_SSA_BAD_KEY = 1, 2, 4, 8
+(VK_COLONY_MASS, VK_COLONY_CELL_AREA, VK_COLONY_CX, VK_COLONY_CY, VK_COLONY_SXX, VK_COLONY_SYY, VK_COLONY_SXY,
+ VK_COLONY_ANGLE, VK_COLONY_MAJOR, VK_COLONY_MINOR) = range(10)
+VK_COLONY_ROWS = 10
+VK_COLONIES_TOO_LONG, VK_COLONIES_GAVE_UP = 1, 2
 VK_GROWTH_PROTEIN, VK_GROWTH_MASS = 0, 1
 VK_RNG_STREAM, VK_RNG_PHILOX = 0, 1
 VK_DIVIDE_SET, VK_DIVIDE_SPLIT, VK_DIVIDE_ZERO = 0, 1, 2
@@ -127,6 +132,11 @@ class VkContactParams(ctypes.Structure):
 class VkContactChannels(ctypes.Structure):
     _fields_ = [(n, ctypes.c_double) for n in ('height', 'space', 'spacer')] + [
         ('n_lines', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
+class VkColoniesParams(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('gx', 'gy', 'min_cells', 'reserved')] + [
+        (n, ctypes.c_double) for n in ('max_length', 'width', 'length', 'link_gap', 'mass')]
 
 
 class VkResponseTable(ctypes.Structure):
@@ -217,6 +227,9 @@ _SIGS = {
     'vk_contact_step_channels': ([ctypes.POINTER(VkContactParams), _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32,
                                   _i32, _f64, _f64, _vp, _vp, _vp, _i64, ctypes.POINTER(VkContactChannels), _vp, _vp],
                                  ctypes.c_int),
+    'vk_colonies_scratch_bytes': ([_i64, _i64], ctypes.c_int64),
+    'vk_colony_metrics': ([ctypes.POINTER(VkColoniesParams), _i64, _i64, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _vp, _vp,
+                           _vp, _vp, _vp, _vp, _vp, _i64, _vp], ctypes.c_int),
     'vk_population_scratch_bytes': ([_i64], ctypes.c_int64),
     'vk_population_plan': ([_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     'vk_response_begin': ([ctypes.POINTER(VkResponseTable), _i64, _i64, _f64] + [_vp] * 14, ctypes.c_int),
