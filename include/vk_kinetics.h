@@ -730,6 +730,72 @@ int vk_flagella_step(const vk_motility_params *p, const vk_flagella_params *f, i
                      int32_t *bin_lin, int32_t *ix_out, vk_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Static fields: analytic gradients (the reference's chemotaxis experiment runs
+ * on these, not on a diffusing lattice)
+ *
+ *   vk_gradient_fill
+ *       replaces make_gradient (vivarium/processes/diffusion_field.py:42-206):
+ *       the initial planes of a lattice, evaluated at the middle of every bin.
+ *   vk_static_gather
+ *       replaces StaticField.next_update / get_concentration (vivarium/
+ *       processes/static_field.py:79-119): the field at every agent's own
+ *       continuous location.
+ *   vk_motility_step_static, vk_flagella_step_static
+ *       the motile steps with that field sensed at the agent's position at every
+ *       inner update instead of a lattice plane at its bin.
+ * All four evaluate one device function in the reference's operation order:
+ *   dx = x - cx; dy = y - cy; d = sqrt(dx*dx + dy*dy) / 1000.0   (um -> mm)
+ *   uniform p0 | gaussian exp((-(d*d)) / (2.0 * (p0*p0))) | linear p0 + p1 * d |
+ *   exponential p1 * pow(p0, d)
+ * +, -, x, / and sqrt round as the reference's doubles do; exp and pow are the
+ * device library's.  The gaussian has no base factor: its value lies in (0, 1].
+ * ------------------------------------------------------------------------- */
+
+enum { VK_GRADIENT_UNIFORM = 0, VK_GRADIENT_GAUSSIAN = 1, VK_GRADIENT_LINEAR = 2, VK_GRADIENT_EXPONENTIAL = 3 };
+typedef struct { int32_t type; double cx, cy; double p0, p1; } vk_gradient_spec;
+/* uniform: p0 = value.  gaussian: p0 = deviation.  linear: p0 = base, p1 = slope.
+   exponential: p0 = base, p1 = scale.  cx, cy are in um: center[i] * bounds[i],
+   multiplied on the host in Python doubles as the reference does. */
+#define VK_GRADIENT_MAX 8      /* specs passed by value per launch */
+
+/* Every entry point below refuses (VK_ERR_ARG) a spec it would evaluate whose type
+ * is unknown, a gaussian with deviation 0 and an exponential with base <= 0.   */
+
+/* planes[f*plane_stride + ix*row_stride + iy] = value of specs[f] at
+ * (((ix + 0.5) * bound_x) / nx, ((iy + 0.5) * bound_y) / ny) for f < n_specs
+ * (<= VK_GRADIENT_MAX), ix < nx (<= 65535), iy < ny (<= row_stride).  specs is a
+ * host array, read during the call.  Nothing else of the planes is written.   */
+int vk_gradient_fill(const vk_gradient_spec *specs, int32_t n_specs, double *planes,
+                     int64_t plane_stride, int64_t row_stride, int32_t nx, int32_t ny,
+                     double bound_x, double bound_y, vk_stream_t stream);
+
+/* conc[row_of[j]*ld_conc + a] = value of specs[field_of[j]] at (loc[a], loc[ld + a])
+ * for j < n_map (<= VK_GRADIENT_MAX) and a < n.  specs, field_of (each in [0,
+ * VK_GRADIENT_MAX)) and row_of are host arrays, read during the call; loc ([2][ld])
+ * and conc are device arrays.  Columns >= n and unmapped rows are not written. */
+int vk_static_gather(const vk_gradient_spec *specs, const int32_t *field_of, const int32_t *row_of,
+                     int32_t n_map, const double *loc, int64_t ld, int64_t n_agents, double *conc,
+                     int64_t ld_conc, vk_stream_t stream);
+
+/* vk_motility_step / vk_flagella_step with an analytic ligand: *ligand (a host
+ * struct, read during the call) is evaluated at the agent's position at every
+ * inner update -- at the position the previous inner update left, which is where
+ * the reference's deriver order puts it.  Everything else (receptor, motor,
+ * draws, move, bins, counter) is the same kernel body; nx, ny and the bounds
+ * still give the bins that are emitted.                                       */
+int vk_motility_step_static(const vk_motility_params *p, int64_t n_agents, int64_t ld, double dt,
+                            int32_t substeps, double *motil, double *loc, const int64_t *key,
+                            const vk_gradient_spec *ligand, int32_t nx, int32_t ny, double bound_x,
+                            double bound_y, uint64_t *counter, int32_t *bin_lin, int32_t *ix_out,
+                            vk_stream_t stream);
+int vk_flagella_step_static(const vk_motility_params *p, const vk_flagella_params *f, int64_t n_agents,
+                            int64_t ld, double dt, int32_t substeps, double *motil, double *flag,
+                            int32_t *flag_int, double *loc, const int64_t *key,
+                            const vk_gradient_spec *ligand, int32_t nx, int32_t ny, double bound_x,
+                            double bound_y, uint64_t *counter, int32_t *bin_lin, int32_t *ix_out,
+                            vk_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Motile agents that grow and divide (the reference's ChemotaxisODEExpressionFlagella,
  * vivarium/compartments/chemotaxis_flagella.py:94-173)
  *

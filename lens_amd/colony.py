@@ -15,6 +15,11 @@ a :class:`~lens_amd.lattice.Lattice` (configs 3-4; DiffusionField + agents)
     kinetics (external from the previous step: the reference's one-step lag)
     -> gather external := pre-step field at the agent's bin
     -> diffusion substeps -> exchange scatter in agent order.
+a :class:`~lens_amd.static_field.StaticField` (the reference's static lattice without its
+multibody; vivarium/processes/static_field.py)
+    kinetics (external from the previous step) -> external := the analytic gradient at the
+    agent's own position (vk_static_gather).  No field store: exchange counts are dropped.
+    A motile colony senses the gradient where it is (the _static launches), not a bin.
 
 Step order and quirks follow SURVEY.md Appendix A.5.
 
@@ -96,6 +101,7 @@ from lens_amd.motility import (DeviceOccupancy, DIVISION_MODES, MotilityModel, R
                                FLAGI_ROW_NAMES, check_flagella_counts, flagella_step, motility_step)
 from lens_amd.rate_law_compiler import compile_rate_laws, RateLawTable
 from lens_amd.response import CellResponse, ResponseBuffers, ResponseEngine
+from lens_amd.static_field import StaticField
 from lens_amd.stochastic import StochasticEngine, StochasticModel, describe_status, divide_counts, flagella_target
 
 
@@ -144,6 +150,7 @@ CAPACITY_SCRATCH = ('bin_lin', 'bin_ix', 'env_bins', 'outflow', '_flag_expr_upda
 class Colony:
     # optional state that a colony may never get (and that objects made by Colony.__new__ lack)
     location = ordinal = env_fields = None       # set with a lattice / by the router / nonspatial
+    static = None                                # Colony(environment=StaticField(...))
     agent_order = None       # sort_by_bin: the reference index of the agent in each column
     attempts = None          # count_attempts
     _flag_expression = _flag_flags = None        # FlagellaModel(expression=...) / (complexes=...)
@@ -164,12 +171,28 @@ class Colony:
             raise ValueError('integrator must be euler or dopri5')
         if exchange not in ('sorted', 'atomic'):
             raise ValueError('exchange must be sorted or atomic')
-        if motility is not None:
+        static = environment if isinstance(environment, StaticField) else None
+        if static is not None:
+            # checked before anything is built: a static field is the reference's static lattice
+            # without its multibody -- there is no field store to exchange with and nothing
+            # that places a capsule or a daughter
+            for given, what, why in (
+                    (mechanics, 'mechanics', 'capsules push each other on a Lattice plane'),
+                    (response, 'response', 'the membrane needs a field to exchange with'),
+                    (cells, 'cells', 'growth and division are out of scope on a static field'),
+                    (stochastic, 'stochastic', 'the stochastic network is out of scope on a static field')):
+                if given is not None:
+                    raise ValueError('a StaticField environment takes no %s= (%s)' % (what, why))
+            if motility is not None and motility.ligand_id not in static.gradient_molecules:
+                raise ValueError('motility: the static field has no gradient of %r (gradient molecules: %s)' % (
+                    motility.ligand_id, static.gradient_molecules))
+        if motility is not None and static is None:
             # checked before anything is built: a motile colony moves and re-bins its
             # agents on the device, on one whole plane (row bands: not yet; division when the
             # model says how the motile state divides)
             if not isinstance(environment, Lattice):
-                raise ValueError('motility needs a Lattice environment (agents move through its ligand plane)')
+                raise ValueError('motility needs a Lattice environment (agents move through its ligand plane) or a '
+                                 'StaticField (they sense its gradient where they are)')
             if motility.ligand_id not in environment.molecules:
                 raise ValueError('motility: the lattice has no %r plane (molecules: %s)' % (
                     motility.ligand_id, environment.molecules))
@@ -288,6 +311,7 @@ class Colony:
         self.step_index = 0
         self._layout = 0             # bumped when buffers are reallocated (Colony.capture checks it)
         self.lattice: Optional[Lattice] = None
+        self.static: Optional[StaticField] = static
         self.router = None       # distributed.AgentRouter (row-banded multi-rank lattice colonies)
         self.cells = cells
         self.motility = motility
@@ -320,9 +344,14 @@ class Colony:
             self._n_out = torch.zeros(1, dtype=torch.int64, device=dev)
             self._overflow = torch.zeros(1, dtype=torch.int32, device=dev)
         self.environment = environment
-        if isinstance(environment, Lattice):
-            self.lattice = environment
-            self._setup_maps(self.lattice.molecules)
+        if isinstance(environment, (Lattice, StaticField)):
+            if static is None:
+                self.lattice = environment
+            self._setup_maps(environment.molecules)
+            if static is not None:
+                # the deriver's update holds the gradient's molecules only: {molecule: conc row}
+                self._static_rows = {m: t.species.index(('external', m)) for m in static.gradient_molecules
+                                     if ('external', m) in t.species}
             self.location = z(2, ld)
             if motility is not None:
                 self.motil = torch.from_numpy(motility.initial_rows(self.n, ld)).to(dev).contiguous()
@@ -369,10 +398,12 @@ class Colony:
             bin_volume = (depth_um * 1.0 * 1.0) * 1e-15 / 1    # get_bin_volume([1,1],[1,1],depth)
             self.env_binvol_avogadro = bin_volume * avogadro
         elif environment != 'held':
-            raise ValueError('environment must be held, nonspatial or a Lattice')
+            raise ValueError('environment must be held, nonspatial, a Lattice or a StaticField')
         self._capacity_scratch()
         if self.env_fields is not None:
             self._env_to_external()          # derivers run once at t = 0
+        if static is not None:
+            self._static_refresh()           # derivers run once at t = 0
         if response is not None and self.lattice is not None and exchange == 'sorted':
             # the occupancy of the initial bins (set_agents(location=...) rebuilds it)
             lat = self.lattice
@@ -385,8 +416,9 @@ class Colony:
         distributed.install_agents; captured graphs hold the old buffers, so ``_layout`` moves."""
         ld, dev, lat = self.ld, self.device, self.lattice
         i32 = lambda: torch.zeros(ld, dtype=torch.int32, device=dev)
-        if lat is not None:
+        if lat is not None or getattr(self, 'static', None) is not None:   # a borrowed hook: see stochastic below
             self.bin_lin, self.bin_ix = i32(), i32()
+        if lat is not None:
             if self.motility is not None or self.mechanics is not None or self.response is not None:
                 # these colonies exchange in agent order through an occupancy built on the device
                 self._occ_dev = DeviceOccupancy(ld, dev)
@@ -471,10 +503,13 @@ class Colony:
             put(self.env_fields, environment)
             self._env_to_external()
         if location is not None:
-            if self.lattice is None:
-                raise ValueError('locations need a lattice environment')
+            if self.lattice is None and self.static is None:
+                raise ValueError('locations need a lattice or a static field environment')
             put(self.location, location)
-            self.refresh_bins()
+            if self.static is not None:
+                self._static_refresh()
+            else:
+                self.refresh_bins()
 
     def set_flagella(self, counts):
         """The flagella count each agent is to have (the reference's ``internal_counts``
@@ -620,6 +655,19 @@ class Colony:
     def gather_external(self):
         """external := field at the agent's bin (get_local_environments)."""
         self.lattice.gather(self.bin_lin, self.n, self.map_gather_field, self.map_gather_row, self.conc)
+
+    def _static_gather(self):
+        """external := the static field at the agent's own position (StaticField.next_update)."""
+        self.static.gather(self.location, self.n, self.conc, self._static_rows)
+
+    def _static_refresh(self):
+        """The bins and the externals of the current positions: what the derivers leave at
+        t = 0 and after positions were set.  Buffers stay, captured graphs stay valid."""
+        sf = self.static
+        native.check(native._lib.vk_bin_sites(
+            native.ptr(self.location), self.n, self.ld, sf.n_bins[0], sf.n_bins[1], sf.bounds[0], sf.bounds[1], 0,
+            native.ptr(self.bin_lin), native.ptr(self.bin_ix), native.stream_handle()), 'vk_bin_sites')
+        self._static_gather()
 
     def _env_to_external(self):
         if self.map_gather_field.numel():
@@ -772,6 +820,11 @@ class Colony:
                     native.ptr(self.map_fexch_field), int(self.map_fexch_count.numel()),
                     self.env_binvol_avogadro, native.stream_handle()), 'vk_exchange_atomic_f64')
             self._env_to_external()
+        elif self.static is not None:
+            # the field deriver, after the move and the kinetics: the next step's kinetics reads
+            # the field where this step left the agent.  Exchange counts are computed and
+            # dropped, as with 'held': the reference's static lattice has no field store
+            self._static_gather()
         self._finish_step(dt)
         if stamp is not None:
             stamp(2)
@@ -793,6 +846,9 @@ class Colony:
         ``run(dt, dt, dt)`` equals :meth:`step` (dt) bit for bit.  A row-banded
         colony passes ``halo_exchange`` / ``allreduce`` as to :meth:`step`.
         Cells (growth / division) step with :meth:`step`."""
+        if self.static is not None:
+            raise ValueError('run() schedules a diffusing lattice; a colony in a StaticField steps with step() '
+                             '(its field deriver runs on the step clock)')
         if self.lattice is None:
             raise ValueError('run() schedules a lattice colony; use step() otherwise')
         if self.cells is not None:
@@ -886,22 +942,25 @@ class Colony:
         """First in a motile colony's step: sense the pre-step ligand plane, receptor,
         motor, move (vk_motility_step; bins come out of the kernel), then the device
         occupancy of the new bins for the ordered exchange.  No host read and no
-        re-layout: ``_layout`` stays, captured graphs stay valid."""
+        re-layout: ``_layout`` stays, captured graphs stay valid.  In a StaticField the
+        ligand is its gradient at the agent's position (the _static launches), and there is
+        no exchange to order."""
         if self.router is not None:
             raise ValueError('a motile colony takes no router')
+        field = self.lattice if self.static is None else self.static
         # a dividing colony draws by the agent's own key; its column order is the reference's
         # agent order, which the occupancy below keeps (key None)
         key = self.motile_key if self.cells is not None else self.agent_order
         if self.motility.flagella is not None:
-            flagella_step(self.motility, self.lattice, self.location, self.motil, self.flag, self.flag_int, self.n,
+            flagella_step(self.motility, field, self.location, self.motil, self.flag, self.flag_int, self.n,
                           dt, self._motil_counter, key=key, bin_lin=self.bin_lin, bin_ix=self.bin_ix)
         else:
-            motility_step(self.motility, self.lattice, self.location, self.motil, self.n, dt, self._motil_counter,
+            motility_step(self.motility, field, self.location, self.motil, self.n, dt, self._motil_counter,
                           key=key, bin_lin=self.bin_lin, bin_ix=self.bin_ix)
         if self.cells is not None:
             # one heading: a device row copy in stream order
             self.cell[native.VK_CELL_ANGLE, :self.n].copy_(self.motil[native.VK_MOTIL_ANGLE, :self.n])
-        if self.exchange_mode == 'sorted' and self.map_exch_count.numel():
+        if self.static is None and self.exchange_mode == 'sorted' and self.map_exch_count.numel():
             lat = self.lattice
             self._occ_dev.sort(self.bin_lin, self.n, lat.rows_local * lat.ny, self.agent_order)
 

@@ -244,7 +244,8 @@ def mother_machine(n_agents=3, bounds=(20.0, 20.0), n_bins=(10, 10), channel_spa
     [n], ``length``, ``width``, ``volume`` (fL) and ``mass`` (fg at DeriveGlobals'
     density of 1100 g/L: the CellModel's ``initial_mass``), ``growth_rate``,
     ``division_volume``, ``jitter_force``, and the diffusion field's ``molecules``,
-    ``diffusion`` and ``gradient``."""
+    ``diffusion`` and ``gradient``.  The ``gradient`` goes as it is to
+    ``Lattice(..., gradient=)``, which fills the planes as the reference's make_gradient does."""
     bounds = (float(bounds[0]), float(bounds[1]))
     if channel_height is None:
         channel_height = 0.7 * bounds[1]
@@ -268,6 +269,33 @@ def mother_machine(n_agents=3, bounds=(20.0, 20.0), n_bins=(10, 10), channel_spa
         'molecules': ['glc'], 'diffusion': 5e-3,
         'gradient': {'type': 'gaussian', 'molecules': {'glc': {'center': [0.5, 0.5], 'deviation': 3}}},
     }
+
+
+def chemotaxis_static(gradient='exponential', n_agents=1, seed=SEED, n_bins=(10, 10), **motility):
+    """The reference's chemotaxis experiment (vivarium/experiments/chemotaxis.py:70-136): a
+    static field of ``glc__D_e`` over bounds [1000, 3000] um centred at [0.5, 0.0] --
+    exponential with scale 4.0 and base 1.3e2, or linear with base 1e-1 and slope 1.0 -- and
+    ``n_agents`` agents at [0.5, 0.1] x bounds whose receptors start adapted to the field
+    there (``initial_ligand = StaticField.value``).  Returns a dict: ``field`` (the
+    StaticField, a ``Colony(environment=)``), ``motility`` (the MotilityModel; further keyword
+    arguments such as ``substeps`` or ``flagella`` go to it), ``location`` [2, n] and
+    ``bounds``.  The field and the sensing are the reference's; the kinematics are not."""
+    from lens_amd.motility import MotilityModel
+    from lens_amd.static_field import StaticField
+    ligand, bounds, center = 'glc__D_e', [1000, 3000], [0.5, 0.0]
+    if gradient == 'exponential':
+        spec = {'center': center, 'scale': 4.0, 'base': 1.3e2}
+    elif gradient == 'linear':
+        spec = {'base': 1e-1, 'center': center, 'slope': 1.0}
+    else:
+        raise ValueError("chemotaxis_static: gradient must be 'exponential' or 'linear' (got %r)" % (gradient,))
+    field = StaticField([ligand], bounds, {'type': gradient, 'molecules': {ligand: spec}}, n_bins=n_bins)
+    x, y = 0.5 * bounds[0], 0.1 * bounds[1]
+    motility.setdefault('ligand_id', ligand)
+    motility.setdefault('initial_ligand', field.value(ligand, x, y))
+    motility.setdefault('seed', seed)
+    location = np.ascontiguousarray(np.repeat(np.array([[x], [y]]), int(n_agents), axis=1))
+    return {'field': field, 'motility': MotilityModel(**motility), 'location': location, 'bounds': bounds}
 
 
 def chemotaxis_variable_flagella(n_flagella=5, **motility):

@@ -35,10 +35,11 @@
 
 #include "vk_motile.h"
 
+template <class Sense>
 __global__ __launch_bounds__(256) void k_flagella_step(
     vk_motility_params p, vk_flagella_params f, int64_t n, int64_t ld, double h, double amp, int substeps,
     double *__restrict__ motil, double *__restrict__ flag, int32_t *__restrict__ flag_int, double *__restrict__ loc,
-    const int64_t *__restrict__ key, const double *__restrict__ ligand, int nx, int ny, double bx, double by,
+    const int64_t *__restrict__ key, Sense sense, int nx, int ny, double bx, double by,
     double bx_below, double by_below, const uint64_t *__restrict__ counter, int32_t *__restrict__ bin_lin,
     int32_t *__restrict__ ix_out) {
     const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(256) void k_flagella_step(
     double thrust = 0.0, torque = 0.0;
     for (int s = 0; s < substeps; ++s) {
         // (a) sense, (b) receptor: the coarse kernel's
-        const double L = ligand[bin];
+        const double L = motile_sense(sense, bin, x, y);
         motile_receptor(p, CheR, CheB, L, h, n_methyl, P_on);
         const uint64_t step = s0 + (uint64_t)s;
 
@@ -133,23 +134,24 @@ __global__ __launch_bounds__(256) void k_flagella_step(
     if (ix_out) ix_out[a] = ix;
 }
 
-extern "C" int vk_flagella_step(const vk_motility_params *p, const vk_flagella_params *f, int64_t n, int64_t ld,
-                                double dt, int32_t substeps, double *motil, double *flag, int32_t *flag_int,
-                                double *loc, const int64_t *key, const double *ligand, int32_t nx, int32_t ny,
-                                double bound_x, double bound_y, uint64_t *counter, int32_t *bin_lin, int32_t *ix_out,
-                                vk_stream_t stream) {
+// the launch both entry points share: the agents' kernel, then the counter
+template <class Sense>
+static int flagella_launch(const char *what, const vk_motility_params *p, const vk_flagella_params *f, int64_t n,
+                           int64_t ld, double dt, int32_t substeps, double *motil, double *flag, int32_t *flag_int,
+                           double *loc, const int64_t *key, const Sense &sense, int32_t nx, int32_t ny, double bound_x,
+                           double bound_y, uint64_t *counter, int32_t *bin_lin, int32_t *ix_out, vk_stream_t stream) {
     if (!p || !f || n < 0 || ld < n || substeps < 1 || !(dt > 0.0) || nx <= 0 || ny <= 0 || !(bound_x > 0.0) ||
         !(bound_y > 0.0) || (int64_t)nx * ny >= INT32_MAX || !counter || !(f->tau > 0.0) || !(f->sigma2_Y >= 0.0) ||
-        (n > 0 && (!motil || !flag || !flag_int || !loc || !ligand || !bin_lin))) {
-        vk::set_error("vk_flagella_step: bad arguments");
+        (n > 0 && (!motil || !flag || !flag_int || !loc || !bin_lin))) {
+        vk::set_error("%s: bad arguments", what);
         return VK_ERR_ARG;
     }
     hipStream_t s = (hipStream_t)stream;
     if (n > 0) {
         const double h = dt / substeps;
         const double amp = sqrt(f->sigma2_Y) * sqrt(2.0 * h / f->tau);
-        hipLaunchKernelGGL(k_flagella_step, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, *p, *f, n, ld, h, amp,
-                           substeps, motil, flag, flag_int, loc, key, ligand, nx, ny, bound_x, bound_y,
+        hipLaunchKernelGGL(k_flagella_step<Sense>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, *p, *f, n, ld,
+                           h, amp, substeps, motil, flag, flag_int, loc, key, sense, nx, ny, bound_x, bound_y,
                            nextafter(bound_x, 0.0), nextafter(bound_y, 0.0), counter, bin_lin, ix_out);
         const int rc = vk::launch_check("k_flagella_step");
         if (rc) return rc;
@@ -157,4 +159,31 @@ extern "C" int vk_flagella_step(const vk_motility_params *p, const vk_flagella_p
     // the counter advances for an empty colony too: s counts inner updates, not agents
     hipLaunchKernelGGL(k_motile_advance, dim3(1), dim3(64), 0, s, counter, (uint64_t)substeps);
     return vk::launch_check("k_motile_advance");
+}
+
+extern "C" int vk_flagella_step(const vk_motility_params *p, const vk_flagella_params *f, int64_t n, int64_t ld,
+                                double dt, int32_t substeps, double *motil, double *flag, int32_t *flag_int,
+                                double *loc, const int64_t *key, const double *ligand, int32_t nx, int32_t ny,
+                                double bound_x, double bound_y, uint64_t *counter, int32_t *bin_lin, int32_t *ix_out,
+                                vk_stream_t stream) {
+    if (n > 0 && !ligand) {
+        vk::set_error("vk_flagella_step: bad arguments");
+        return VK_ERR_ARG;
+    }
+    return flagella_launch<sense_plane>("vk_flagella_step", p, f, n, ld, dt, substeps, motil, flag, flag_int, loc, key,
+                           sense_plane(ligand), nx, ny, bound_x, bound_y, counter, bin_lin, ix_out, stream);
+}
+
+extern "C" int vk_flagella_step_static(const vk_motility_params *p, const vk_flagella_params *f, int64_t n,
+                                       int64_t ld, double dt, int32_t substeps, double *motil, double *flag,
+                                       int32_t *flag_int, double *loc, const int64_t *key,
+                                       const vk_gradient_spec *ligand, int32_t nx, int32_t ny, double bound_x,
+                                       double bound_y, uint64_t *counter, int32_t *bin_lin, int32_t *ix_out,
+                                       vk_stream_t stream) {
+    if (!ligand || !gradient_spec_ok(*ligand)) {
+        vk::set_error("vk_flagella_step_static: bad arguments");
+        return VK_ERR_ARG;
+    }
+    return flagella_launch<sense_static>("vk_flagella_step_static", p, f, n, ld, dt, substeps, motil, flag, flag_int, loc, key,
+                           *ligand, nx, ny, bound_x, bound_y, counter, bin_lin, ix_out, stream);
 }

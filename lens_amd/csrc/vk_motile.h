@@ -10,8 +10,22 @@
 #include <stdint.h>
 
 #include "vk_bin.h"
+#include "vk_gradient.h"
 #include "vk_internal.h"
 #include "vk_philox.h"
+
+// What an agent senses at an inner update, the kernels' one template parameter: the ligand
+// plane ([nx][ny], whole and unbanded, not written here) at the agent's bin, or an analytic
+// gradient at the agent's own position (the reference's StaticField deriver, which runs after
+// every update of receptor, motor and body: the value is the field where the previous inner
+// update left the agent).  The plane stays a plain restrict pointer in the kernel's
+// arguments, as it was before there was a choice.
+typedef const double *__restrict__ sense_plane;
+typedef vk_gradient_spec sense_static;
+__device__ __forceinline__ double motile_sense(sense_plane ligand, int32_t bin, double, double) { return ligand[bin]; }
+__device__ __forceinline__ double motile_sense(const sense_static &g, int32_t, double x, double y) {
+    return gradient_value(g, x, y);
+}
 
 // ReceptorCluster.next_update (vivarium/processes/chemoreceptor_cluster.py:166-209) at ligand
 // concentration L over h seconds; CheR / CheB already in uM.  The reference's quirk is kept:

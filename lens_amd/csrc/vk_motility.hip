@@ -26,13 +26,16 @@
 //
 // A streaming kernel: per agent it reads and writes 9 state rows and the location once, and
 // reads one ligand value per inner update; the state of an agent lives in registers between.
+// vk_motility_step_static is the same kernel body with the sensing swapped (vk_motile.h): the
+// ligand is an analytic gradient evaluated at the agent's position, nothing is read per update.
 
 #include "vk_motile.h"
 
+template <class Sense>
 __global__ __launch_bounds__(256) void k_motility_step(vk_motility_params p, int64_t n, int64_t ld, double h,
                                                        int substeps, double *__restrict__ motil,
                                                        double *__restrict__ loc, const int64_t *__restrict__ key,
-                                                       const double *__restrict__ ligand, int nx, int ny, double bx,
+                                                       Sense sense, int nx, int ny, double bx,
                                                        double by, double bx_below, double by_below,
                                                        const uint64_t *__restrict__ counter,
                                                        int32_t *__restrict__ bin_lin, int32_t *__restrict__ ix_out) {
@@ -55,8 +58,9 @@ __global__ __launch_bounds__(256) void k_motility_step(vk_motility_params p, int
     // mM -> uM (see the header: the reference's pint conversion, unpinned)
     const double CheR = p.CheR * 1e3, CheB = p.CheB * 1e3;
     for (int s = 0; s < substeps; ++s) {
-        // (a) sense: the plane is not written here, so this is the pre-step field
-        const double L = ligand[bin];
+        // (a) sense (vk_motile.h): a plane is not written here, so this is the pre-step field; an
+        // analytic field is read where the previous inner update left the agent
+        const double L = motile_sense(sense, bin, x, y);
 
         // (b) receptor (vk_motile.h; the clamp quirk is kept there)
         motile_receptor(p, CheR, CheB, L, h, n_methyl, P_on);
@@ -103,20 +107,21 @@ __global__ __launch_bounds__(256) void k_motility_step(vk_motility_params p, int
     if (ix_out) ix_out[a] = ix;
 }
 
-extern "C" int vk_motility_step(const vk_motility_params *p, int64_t n, int64_t ld, double dt, int32_t substeps,
-                                double *motil, double *loc, const int64_t *key, const double *ligand, int32_t nx,
-                                int32_t ny, double bound_x, double bound_y, uint64_t *counter, int32_t *bin_lin,
-                                int32_t *ix_out, vk_stream_t stream) {
+// the launch both entry points share: the agents' kernel, then the counter
+template <class Sense>
+static int motility_launch(const char *what, const vk_motility_params *p, int64_t n, int64_t ld, double dt,
+                           int32_t substeps, double *motil, double *loc, const int64_t *key, const Sense &sense,
+                           int32_t nx, int32_t ny, double bound_x, double bound_y, uint64_t *counter,
+                           int32_t *bin_lin, int32_t *ix_out, vk_stream_t stream) {
     if (!p || n < 0 || ld < n || substeps < 1 || !(dt > 0.0) || nx <= 0 || ny <= 0 || !(bound_x > 0.0) ||
-        !(bound_y > 0.0) || (int64_t)nx * ny >= INT32_MAX || !counter ||
-        (n > 0 && (!motil || !loc || !ligand || !bin_lin))) {
-        vk::set_error("vk_motility_step: bad arguments");
+        !(bound_y > 0.0) || (int64_t)nx * ny >= INT32_MAX || !counter || (n > 0 && (!motil || !loc || !bin_lin))) {
+        vk::set_error("%s: bad arguments", what);
         return VK_ERR_ARG;
     }
     hipStream_t s = (hipStream_t)stream;
     if (n > 0) {
-        hipLaunchKernelGGL(k_motility_step, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, *p, n, ld,
-                           dt / substeps, substeps, motil, loc, key, ligand, nx, ny, bound_x, bound_y,
+        hipLaunchKernelGGL(k_motility_step<Sense>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, *p, n, ld,
+                           dt / substeps, substeps, motil, loc, key, sense, nx, ny, bound_x, bound_y,
                            nextafter(bound_x, 0.0), nextafter(bound_y, 0.0), counter, bin_lin, ix_out);
         const int rc = vk::launch_check("k_motility_step");
         if (rc) return rc;
@@ -124,4 +129,29 @@ extern "C" int vk_motility_step(const vk_motility_params *p, int64_t n, int64_t 
     // the counter advances for an empty colony too: s counts inner updates, not agents
     hipLaunchKernelGGL(k_motile_advance, dim3(1), dim3(64), 0, s, counter, (uint64_t)substeps);
     return vk::launch_check("k_motile_advance");
+}
+
+extern "C" int vk_motility_step(const vk_motility_params *p, int64_t n, int64_t ld, double dt, int32_t substeps,
+                                double *motil, double *loc, const int64_t *key, const double *ligand, int32_t nx,
+                                int32_t ny, double bound_x, double bound_y, uint64_t *counter, int32_t *bin_lin,
+                                int32_t *ix_out, vk_stream_t stream) {
+    if (n > 0 && !ligand) {
+        vk::set_error("vk_motility_step: bad arguments");
+        return VK_ERR_ARG;
+    }
+    return motility_launch<sense_plane>("vk_motility_step", p, n, ld, dt, substeps, motil, loc, key, sense_plane(ligand), nx, ny,
+                           bound_x, bound_y, counter, bin_lin, ix_out, stream);
+}
+
+extern "C" int vk_motility_step_static(const vk_motility_params *p, int64_t n, int64_t ld, double dt,
+                                       int32_t substeps, double *motil, double *loc, const int64_t *key,
+                                       const vk_gradient_spec *ligand, int32_t nx, int32_t ny, double bound_x,
+                                       double bound_y, uint64_t *counter, int32_t *bin_lin, int32_t *ix_out,
+                                       vk_stream_t stream) {
+    if (!ligand || !gradient_spec_ok(*ligand)) {
+        vk::set_error("vk_motility_step_static: bad arguments");
+        return VK_ERR_ARG;
+    }
+    return motility_launch<sense_static>("vk_motility_step_static", p, n, ld, dt, substeps, motil, loc, key, *ligand,
+                           nx, ny, bound_x, bound_y, counter, bin_lin, ix_out, stream);
 }

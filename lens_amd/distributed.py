@@ -157,6 +157,9 @@ class AgentRouter:
         if getattr(col, 'stochastic', None) is not None:
             raise ValueError('AgentRouter: a colony with stochastic kinetics (Colony(stochastic=...)) takes no '
                              'router: its draw keys are not global across ranks')
+        if getattr(col, 'static', None) is not None:
+            raise ValueError('AgentRouter: a colony in a StaticField takes no router: there are no row bands to '
+                             'route between')
         lat = col.lattice
         bands = row_bands(lat.n_bins[0], world)
         if (lat.row_lo_global, lat.row_hi_global) != bands[rank]:

@@ -96,7 +96,7 @@ def stencil_bands(bands: int = -1, top_rows: int = 0) -> int:
 class Lattice:
     def __init__(self, molecules: Sequence[str], n_bins, bounds, depth: float, diffusion: float,
                  device=None, row_band=None, halo: int = 0, avogadro: float = N_A_LEGACY,
-                 initial=None):
+                 initial=None, gradient=None):
         native.load()            # no CPU fallback: the kernels or an error
         self.molecules = list(molecules)
         self.n_bins = [int(n_bins[0]), int(n_bins[1])]
@@ -145,6 +145,14 @@ class Lattice:
                     self.set_field(m, initial[m])
         else:
             self.fields.fill_(1.0)   # DiffusionField.ones_field default (diffusion_field.py:381-382)
+        if gradient:
+            # initial_state.update(make_gradient(...)) (diffusion_field.py:266-270): the gradient's
+            # planes overwrite the named molecules, whatever `initial` gave them
+            from lens_amd.static_field import make_gradient
+            for m, plane in make_gradient(gradient, self.n_bins, self.bounds, self.device).items():
+                if m not in self.molecules:
+                    raise ValueError('gradient molecule %r is not one of the molecules %r' % (m, self.molecules))
+                self.set_field(m, plane)
 
     # local row index of the first owned row
     @property

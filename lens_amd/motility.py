@@ -304,23 +304,31 @@ def motility_step(model: MotilityModel, lattice, location, motil, n: int, dt: fl
     inner updates of ``dt / substeps`` for agents [0, n) of ``location`` [2, ld]
     and ``motil`` [VK_MOTIL_ROWS, ld]; ``counter`` (one device int64) supplies
     the inner-update index and is advanced.  ``bin_lin`` / ``bin_ix`` (int32
-    [ld]) receive the bins.  The lattice must hold whole, unbanded planes."""
+    [ld]) receive the bins.  The lattice must hold whole, unbanded planes; a
+    :class:`lens_amd.static_field.StaticField` in its place senses the analytic
+    gradient at each agent's own position (vk_motility_step_static)."""
     import torch
     from lens_amd.lattice import whole_plane
-    if not whole_plane(lattice):
+    from lens_amd.static_field import StaticField
+    static = isinstance(lattice, StaticField)
+    if not static and not whole_plane(lattice):
         raise ValueError('motility_step: a whole, unbanded plane')
     ld = location.shape[1]
     if motil.shape != (native.VK_MOTIL_ROWS, ld) or not (motil.is_contiguous() and location.is_contiguous()):
         raise ValueError('motility_step: motil must be [VK_MOTIL_ROWS, ld] beside location [2, ld], contiguous')
     if bin_lin is None:
         bin_lin = torch.zeros(ld, dtype=torch.int32, device=location.device)
-    plane = lattice.fields[lattice.molecules.index(model.ligand_id)]
     p = model.vk_params()
-    native.check(native._lib.vk_motility_step(
+    if static:
+        launch, ligand = native._lib.vk_motility_step_static, ctypes.byref(lattice.spec(model.ligand_id))
+    else:
+        launch = native._lib.vk_motility_step
+        ligand = native.ptr(lattice.fields[lattice.molecules.index(model.ligand_id)])
+    native.check(launch(
         ctypes.byref(p), n, ld, float(dt), int(model.substeps if substeps is None else substeps), native.ptr(motil),
-        native.ptr(location), native.ptr(key), native.ptr(plane), lattice.n_bins[0], lattice.n_bins[1],
+        native.ptr(location), native.ptr(key), ligand, lattice.n_bins[0], lattice.n_bins[1],
         lattice.bounds[0], lattice.bounds[1], native.ptr(counter), native.ptr(bin_lin), native.ptr(bin_ix),
-        native.stream_handle()), 'vk_motility_step')
+        native.stream_handle()), 'vk_motility_step_static' if static else 'vk_motility_step')
     return bin_lin
 
 
@@ -328,12 +336,15 @@ def flagella_step(model: MotilityModel, lattice, location, motil, flag, flag_int
                   key=None, bin_lin=None, bin_ix=None, substeps: Optional[int] = None):
     """One vk_flagella_step launch on the current stream: :func:`motility_step` with
     ``model.flagella``'s motor in the place of the coarse one, on ``flag``
-    [VK_FLAG_ROWS, ld] (float64) and ``flag_int`` [VK_FLAGI_ROWS, ld] (int32)."""
+    [VK_FLAG_ROWS, ld] (float64) and ``flag_int`` [VK_FLAGI_ROWS, ld] (int32).  A
+    ``StaticField`` in the lattice's place: vk_flagella_step_static."""
     import torch
     from lens_amd.lattice import whole_plane
+    from lens_amd.static_field import StaticField
+    static = isinstance(lattice, StaticField)
     if model.flagella is None:
         raise ValueError('flagella_step: the model has no FlagellaModel')
-    if not whole_plane(lattice):
+    if not static and not whole_plane(lattice):
         raise ValueError('flagella_step: a whole, unbanded plane')
     ld = location.shape[1]
     if motil.shape != (native.VK_MOTIL_ROWS, ld) or not (motil.is_contiguous() and location.is_contiguous()):
@@ -345,13 +356,18 @@ def flagella_step(model: MotilityModel, lattice, location, motil, flag, flag_int
                          '[VK_FLAGI_ROWS, ld], contiguous')
     if bin_lin is None:
         bin_lin = torch.zeros(ld, dtype=torch.int32, device=location.device)
-    plane = lattice.fields[lattice.molecules.index(model.ligand_id)]
     p, f = model.vk_params(), model.flagella.vk_params()
-    native.check(native._lib.vk_flagella_step(
+    if static:
+        launch, ligand = native._lib.vk_flagella_step_static, ctypes.byref(lattice.spec(model.ligand_id))
+    else:
+        launch = native._lib.vk_flagella_step
+        ligand = native.ptr(lattice.fields[lattice.molecules.index(model.ligand_id)])
+    native.check(launch(
         ctypes.byref(p), ctypes.byref(f), n, ld, float(dt), int(model.substeps if substeps is None else substeps),
         native.ptr(motil), native.ptr(flag), native.ptr(flag_int), native.ptr(location), native.ptr(key),
-        native.ptr(plane), lattice.n_bins[0], lattice.n_bins[1], lattice.bounds[0], lattice.bounds[1],
-        native.ptr(counter), native.ptr(bin_lin), native.ptr(bin_ix), native.stream_handle()), 'vk_flagella_step')
+        ligand, lattice.n_bins[0], lattice.n_bins[1], lattice.bounds[0], lattice.bounds[1],
+        native.ptr(counter), native.ptr(bin_lin), native.ptr(bin_ix), native.stream_handle()),
+        'vk_flagella_step_static' if static else 'vk_flagella_step')
     return bin_lin
 
 

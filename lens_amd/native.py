@@ -38,6 +38,7 @@ EXPORTS = (
     'vk_flagella_step', 'vk_flagella_counts', 'vk_divide_flagella',
     'vk_ssa_step', 'vk_ssa_propensities', 'vk_divide_counts', 'vk_ssa_flagella_target',
     'vk_colonies_scratch_bytes', 'vk_colony_metrics',
+    'vk_gradient_fill', 'vk_static_gather', 'vk_motility_step_static', 'vk_flagella_step_static',
 )
 
 VK_CELL_MASS, VK_CELL_VOLUME, VK_CELL_LENGTH, VK_CELL_SURFACE_AREA, VK_CELL_PROTEIN, VK_CELL_ANGLE = range(6)
@@ -59,6 +60,8 @@ VK_SSA_MAX_EVENTS, VK_SSA_NONFINITE, VK_SSA_OVERFLOW, VK_SSA_BAD_KEY = 1, 2, 4, 
  VK_COLONY_ANGLE, VK_COLONY_MAJOR, VK_COLONY_MINOR) = range(10)
 VK_COLONY_ROWS = 10
 VK_COLONIES_TOO_LONG, VK_COLONIES_GAVE_UP = 1, 2
+VK_GRADIENT_UNIFORM, VK_GRADIENT_GAUSSIAN, VK_GRADIENT_LINEAR, VK_GRADIENT_EXPONENTIAL = range(4)
+VK_GRADIENT_MAX = 8
 VK_GROWTH_PROTEIN, VK_GROWTH_MASS = 0, 1
 VK_RNG_STREAM, VK_RNG_PHILOX = 0, 1
 VK_DIVIDE_SET, VK_DIVIDE_SPLIT, VK_DIVIDE_ZERO = 0, 1, 2
@@ -121,6 +124,12 @@ class VkFlagellaParams(ctypes.Structure):
     _fields_ = [(n, ctypes.c_double) for n in (
         'YP_ss', 'sigma2_Y', 'tau', 'K_d', 'H', 'omega', 'g_0', 'g_1', 'K_D', 'flagellum_thrust',
         'tumble_scaling', 'run_scaling')]
+
+
+class VkGradientSpec(ctypes.Structure):
+    """One analytic gradient (vk_gradient_spec): p0, p1 by type, cx, cy in um."""
+    _fields_ = [('type', ctypes.c_int32), ('cx', ctypes.c_double), ('cy', ctypes.c_double),
+                ('p0', ctypes.c_double), ('p1', ctypes.c_double)]
 
 
 class VkContactParams(ctypes.Structure):
@@ -209,6 +218,16 @@ _SIGS = {
                           _f64, _f64, _vp, _vp, _vp, _vp], ctypes.c_int),
     'vk_flagella_step': ([ctypes.POINTER(VkMotilityParams), ctypes.POINTER(VkFlagellaParams), _i64, _i64, _f64, _i32,
                           _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f64, _f64, _vp, _vp, _vp, _vp], ctypes.c_int),
+    'vk_gradient_fill': ([ctypes.POINTER(VkGradientSpec), _i32, _vp, _i64, _i64, _i32, _i32, _f64, _f64, _vp],
+                         ctypes.c_int),
+    'vk_static_gather': ([ctypes.POINTER(VkGradientSpec), _i32p, _i32p, _i32, _vp, _i64, _i64, _vp, _i64, _vp],
+                         ctypes.c_int),
+    'vk_motility_step_static': ([ctypes.POINTER(VkMotilityParams), _i64, _i64, _f64, _i32, _vp, _vp, _vp,
+                                 ctypes.POINTER(VkGradientSpec), _i32, _i32, _f64, _f64, _vp, _vp, _vp, _vp],
+                                ctypes.c_int),
+    'vk_flagella_step_static': ([ctypes.POINTER(VkMotilityParams), ctypes.POINTER(VkFlagellaParams), _i64, _i64, _f64,
+                                 _i32, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(VkGradientSpec), _i32, _i32, _f64, _f64,
+                                 _vp, _vp, _vp, _vp], ctypes.c_int),
     'vk_flagella_counts': ([_i64, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     'vk_divide_flagella': ([_i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32,
                             ctypes.c_uint64, ctypes.c_uint64, _i64, _vp], ctypes.c_int),

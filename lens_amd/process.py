@@ -297,6 +297,11 @@ class BatchedDiffusionField(ProcessBase):
                                device=self.device, avogadro=p['avogadro'])
         self.initial_agents = p['agents']
         self._torch = torch
+        # the reference's initial_state.update(make_gradient(...)) (diffusion_field.py:266-270)
+        self.initial_state = dict(p['initial_state'])
+        if p['gradient']:
+            from lens_amd.static_field import make_gradient
+            self.initial_state.update(make_gradient(p['gradient'], self.n_bins, self.bounds, self.device))
         nf = len(self.molecule_ids)
         self._map = torch.arange(nf, dtype=torch.int32, device=self.device)   # plane f -> row f
 
@@ -316,7 +321,7 @@ class BatchedDiffusionField(ProcessBase):
         schema['agents']['*'] = {'boundary': {
             'location': {'_default': [0.5 * b for b in self.bounds], '_updater': 'set'},
             'external': local}}
-        init = self.parameters['initial_state']
+        init = self.initial_state
         schema['fields'] = {
             m: {'_value': DeviceField(self._device_field(init[m]) if m in init else self.ones_field()),
                 '_updater': 'accumulate', '_emit': True}
@@ -360,3 +365,67 @@ class BatchedDiffusionField(ProcessBase):
 
     def next_update(self, timestep, states):
         return self.next_update_raw(timestep, states).as_dict()
+
+
+class BatchedStaticField(ProcessBase):
+    """GPU drop-in for the ``StaticField`` deriver (vivarium/processes/static_field.py:25-119).
+
+    Same ``name``, ``defaults``, ``ports_schema`` and update dict: every agent's
+    ``boundary.external`` is set to the analytic gradient at its own ``boundary.location``,
+    for the gradient's molecules only.  ``next_update`` packs the locations into one
+    ``[2, n]`` tensor and evaluates them in one ``vk_static_gather``."""
+
+    name = 'static_field'
+    defaults = {
+        'molecules': ['glc'],
+        'n_bins': [10, 10],
+        'bounds': [10, 10],
+        'gradient': {},
+        'boundary_port': 'boundary',
+        'external_key': 'external',
+    }
+
+    def __init__(self, parameters=None):
+        super().__init__(parameters)
+        import torch
+        from lens_amd import native
+        from lens_amd.static_field import StaticField
+        p = self.parameters
+        self.molecules = list(p['molecules'])
+        self.bounds = p['bounds']
+        self.boundary_port = p['boundary_port']
+        self.external_key = p['external_key']
+        self.gradient = p['gradient']
+        self.device = native.resolve_device(p.get('device'))
+        self.field = StaticField(self.molecules, self.bounds, self.gradient, p['n_bins'])
+        self._torch = torch
+
+    def ports_schema(self):
+        local = {m: {'_default': 0.0, '_updater': 'set'} for m in self.molecules}
+        return {'agents': {'*': {self.boundary_port: {
+            'location': {'_default': [0.5 * b for b in self.bounds], '_updater': 'set'},
+            self.external_key: local}}}}
+
+    def next_update_raw(self, timestep, states):
+        """:meth:`next_update`'s update as an :class:`AgentLeafUpdate`."""
+        torch = self._torch
+        agents = states['agents']
+        ids = list(agents)
+        keys = list(self.field.gradient_molecules)
+        rows = []
+        if ids:
+            values_at = getattr(agents, 'values_at', None)      # columnar agents: one column read
+            locs = (values_at((self.boundary_port, 'location'), ids) if values_at is not None else
+                    [agents[a][self.boundary_port]['location'] for a in ids])
+            with torch.cuda.device(self.device):
+                loc = torch.from_numpy(np.ascontiguousarray(np.asarray(locs, dtype=np.float64).T)).to(self.device)
+                vals = torch.empty((len(keys), len(ids)), dtype=torch.float64, device=self.device)
+                self.field.gather(loc, len(ids), vals, {m: j for j, m in enumerate(keys)})
+                rows = vals.cpu().numpy().T.tolist()
+        return AgentLeafUpdate({}, ids, (self.boundary_port, self.external_key), keys, rows)
+
+    def next_update(self, timestep, states):
+        # the reference returns {'agents': {}} for no agents
+        update = self.next_update_raw(timestep, states).as_dict()
+        update.setdefault('agents', {})
+        return update
