@@ -37,7 +37,7 @@
  *   vk_cell_step / vk_divide_*, vk_kremling_step, vk_expression_step,
  *   vk_motility_step, vk_flagella_step, vk_contact_step, vk_contact_step_channels, vk_population_plan,
  *   vk_flagella_counts, vk_divide_flagella, vk_ssa_step, vk_ssa_propensities, vk_divide_counts,
- *   vk_ssa_flagella_target, vk_colony_metrics
+ *   vk_ssa_flagella_target, vk_colony_metrics, vk_translation_step, vk_divide_ribosomes
  *       are introduced by the comment blocks above their declarations.
  *
  * Conventions
@@ -958,6 +958,128 @@ int vk_divide_counts(int64_t n_out, int64_t n_keep, int64_t n_src, const int32_t
  * cleared) when a count was negative or above 32: the motor's mask holds 32 flagella.  */
 int vk_ssa_flagella_target(int64_t n_agents, const int32_t *counts_row, int32_t *target,
                            int32_t *flags, vk_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Stochastic translation: ribosomes elongate on a bounded, ordered per-agent list
+ *
+ *   vk_translation_step
+ *       stands where the reference runs Translation.next_update
+ *       (vivarium/processes/translation.py:423-579) with polymerize_step
+ *       (vivarium/library/polymerize.py:205-259).  Elongation is the reference's,
+ *       operation for operation.  Initiation is the direct method in vk_ssa_step's
+ *       arithmetic and Philox draws, NOT arrow's: trajectories agree with the reference
+ *       in distribution only.  Restated as per-agent Python loops by
+ *       tests/translation_ref.py.
+ *   vk_divide_ribosomes
+ *       THIS ENGINE'S OWN rule: the reference's `ribosomes` store declares no divider.
+ * ------------------------------------------------------------------------- */
+
+#define VK_TL_MAX_SLOTS 128       /* ribosomes per agent: 128 x 64 lanes x 4 B = 32 KiB of LDS   */
+#define VK_TL_MAX_TEMPLATES 64    /* unbound[template][lane]: 16 KiB                             */
+#define VK_TL_MAX_MONOMERS 24     /* limit[monomer][lane]: 6 KiB; 54 KiB and 260 B, under 64 KiB */
+#define VK_TL_MAX_POSITION 0x00ffffff   /* a sequence holds at most 2^24 - 1 residues            */
+
+/* Mixed into the seed of vk_translation_step's draws and of vk_divide_ribosomes' coins. */
+#define VK_TL_DOMAIN 0x746c5f5f73746570ULL
+#define VK_TL_DIVIDE_DOMAIN 0x746c5f5f64697669ULL
+
+/* One ribosome: (position << 7) | (template << 1) | occluding. */
+#define VK_TL_PACK(position, template_index, occluding) \
+    ((int32_t)(((uint32_t)(position) << 7) | ((uint32_t)(template_index) << 1) | ((occluding) ? 1u : 0u)))
+
+enum vk_tl_status {             /* bits OR-ed into the caller's status[] (never cleared)              */
+    VK_TL_SLOTS_FULL = 1,       /* an initiation found the list at capacity: not fired, the agent
+                                   initiates no more this step                                        */
+    VK_TL_BAD_KEY = 2,          /* the agent's key lies outside [0, 2^31): not stepped                */
+    VK_TL_NONFINITE = 4,        /* the summed propensity was inf or NaN: no more initiation this step */
+    VK_TL_OVERFLOW = 8,         /* a count would pass INT32_MAX: see below                            */
+    VK_TL_MAX_EVENTS = 16       /* the agent fired max_events initiations: no more this step          */
+};
+
+enum vk_tl_release { VK_TL_RELEASE_REFERENCE = 0, VK_TL_RELEASE_TEMPLATE = 1 };
+
+/* The model, the same for every agent.  Every pointer is a DEVICE array the caller owns:
+ *   operon_species [n_templates]   row of `counts` that holds the transcript count of template
+ *                                  i's operon (templates are in transcript_order);
+ *   seq_ptr [n_templates + 1], seq monomer index (< n_monomers) of every residue, the templates'
+ *                                  sequences concatenated; the one terminator of template i
+ *                                  stands at its length seq_ptr[i + 1] - seq_ptr[i] >= 1;
+ *   prod_ptr [n_templates + 1], prod_species   rows of `counts` of the terminator's products;
+ *   affinity [n_templates];
+ *   interval [n_plan], elongate [n_plan]   the sub-interval plan of the step (below).          */
+typedef struct {
+    int32_t n_templates, n_monomers, n_species, max_slots;
+    int32_t occlusion, release, ribosome_species, n_plan;
+    const int32_t *operon_species, *seq_ptr, *prod_ptr, *prod_species, *elongate;
+    const uint8_t *seq;
+    const double *affinity, *interval;
+} vk_tl_model;
+
+/* One step for agents [0, n), one agent per lane.  Per agent: her ribosome list slots
+ * [max_slots][ld] (VK_TL_PACK words, entries [0, length[a]) in insertion order), molecules
+ * [n_monomers + 2][ld] (the monomers, then ATP, then ADP) and her column of counts
+ * [n_species][ld], the table vk_ssa_step steps.
+ *
+ *   unbound[i] = counts[operon_species[i]] (the reference's gene - bound with bound = 0: no
+ *                stored ribosome is 'bound', translation.py:444-450, 519-521);
+ *   free = counts[ribosome_species]; limit[m] = molecules[m]; e = 0; events = 0.
+ * The plan is the reference's float loop run once on the host (translation.py:478-499, 533):
+ *   d = 1 / rate; while time < T: interval = min(d, T - time); elongate = (interval == d);
+ *   time += interval.  A trailing partial sub-interval elongates nothing.
+ * Per sub-interval k, in this order:
+ *   1 substrate   ribosomes = free and unbound[] as they are now, before elongation (:480-483);
+ *   2 elongation  if elongate[k], every ribosome in list order (polymerize.py:221-252): with
+ *                 m = seq[seq_ptr[t] + p], if limit[m] > 0: limit[m] -= 1, p += 1, and at
+ *                 p == length of t the ribosome completes: every product of the terminator gains
+ *                 1, free += 1, she leaves the list and the order of the rest is kept.  A
+ *                 ribosome whose monomer is exhausted stalls in place; the earlier in the list
+ *                 takes the last monomer.  A completion that would take a product or free past
+ *                 INT32_MAX is VK_TL_OVERFLOW: it is not made (no monomer taken) and the agent
+ *                 does nothing more this step but the books below;
+ *   3 initiation  the direct method on the substrate over interval[k], clock t = 0; while
+ *                 ribosomes >= 1 (with none nothing binds and no draw is made):
+ *                 a_i = (affinity[i] * (double) unbound[i]) * (double) ribosomes, 0 when either
+ *                 count is < 1 (vk_ssa_step's a_r for first-order reactants);
+ *                 total = a_0 + a_1 + ... in template order, cum_i the running sums;
+ *                 total == 0 ends the sub-interval without a draw; total not finite:
+ *                 VK_TL_NONFINITE; draw e: one Philox4x32-10 block, key (seed ^ VK_TL_DOMAIN),
+ *                 counter (step, (int32) keys[a], e, 0), u1, u2 as vk_ssa_step; e += 1 for
+ *                 every draw made, fired or not;
+ *                 tau = -log(1.0 - u1) / total; t + tau > interval[k] ends the sub-interval, the
+ *                 event is discarded; else t = t + tau and the first q with cum_q > u2 * total
+ *                 fires: unbound[q] -= 1, ribosomes -= 1, free -= 1, VK_TL_PACK(0, q, 1) is
+ *                 appended (it first elongates in sub-interval k + 1), events += 1; a full list:
+ *                 VK_TL_SLOTS_FULL, not fired; events == max_events: VK_TL_MAX_EVENTS;
+ *   4 release     every occluding ribosome with p >= occlusion becomes polymerizing and
+ *                 unbound[r] += 1, r = 0 (VK_TL_RELEASE_REFERENCE: the reference decrements
+ *                 bound[ribosome.template_index], which Translation never sets,
+ *                 translation.py:528-531, polymerize.py:43) or r = t (VK_TL_RELEASE_TEMPLATE).
+ * Then: counts[ribosome_species] = free; molecules[m] = limit[m]; with used = the sum of the
+ * monomers taken, ATP -= 2 used, ADP += 2 used (:552-557; a result outside int32 is clamped with
+ * VK_TL_OVERFLOW); the list and its length are stored.  Entries beyond the length keep stale
+ * words.  Ribosomes found with t >= n_templates or p >= the template's length stall.
+ * step_counter: one device int64, the `step` word; advance != 0 adds one after the launch (also
+ * for n = 0), advance == 0 leaves it to the vk_ssa_step that follows on the same counter.
+ * events_out [ld]: initiations per agent.  Draws depend on (seed, step, key, e) alone.  No
+ * atomics, no host synchronisation, no wait between workgroups.  Bad n, ld, capacity, table
+ * sizes or null pointers return VK_ERR_ARG and launch nothing.                          */
+int vk_translation_step(const vk_tl_model *model, int64_t n_agents, int64_t ld, int32_t *slots,
+                        int32_t *length, int32_t *molecules, int32_t *counts, const int64_t *keys,
+                        uint64_t seed, int64_t *step_counter, int32_t advance, int32_t max_events,
+                        int32_t *events_out, int32_t *status, vk_stream_t stream);
+
+/* The ribosome lists over a plan of vk_divide_plan or vk_population_plan.  Per slot j with
+ * a = src_index[j]: a survivor's list is copied; daughter k takes, in order, every ribosome
+ * i < length_src[a] of the mother with (u < 0.5 ? 0 : 1) == k,
+ * u = Philox(key (seed ^ VK_TL_DIVIDE_DOMAIN); counter (step, (int32) key_src[a], 0, i)): one
+ * coin per (mother, list entry), the same for both daughters.  Entries of the destination
+ * beyond the new length are zeroed.  key_src: the mothers' keys BEFORE vk_divide_counts
+ * renews them.                                                                         */
+int vk_divide_ribosomes(int64_t n_out, int64_t n_src, const int32_t *src_index, const int32_t *kind,
+                        const int32_t *slots_src, const int32_t *length_src, int64_t ld_src,
+                        const int64_t *key_src, int32_t *slots_dst, int32_t *length_dst,
+                        int64_t ld_dst, int32_t max_slots, uint64_t seed, uint64_t step,
+                        vk_stream_t stream);
 
 /* Occupancy on the device: order[k] = the agent column with the k-th smallest
  * (bin_lin[a], key[a]) (key NULL: the column index; keys distinct, < 2^32),

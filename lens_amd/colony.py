@@ -74,6 +74,14 @@ growth and division, the network advances by the Gillespie direct method (vk_ssa
 and division splits the counts with the reference's ``divide_split`` (vk_divide_counts).
 ``FlagellaModel(0, complexes='flagella')`` then takes the flagella count from that species.
 
+With a :class:`~lens_amd.translation.TranslationModel` (``translation=``, beside
+``stochastic=``) every agent also carries an ordered ribosome list (``ribosome_slots``,
+``ribosome_count``) and her monomer, ATP and ADP pools (``tl_molecules``).  Right before the
+network's step the ribosomes elongate and bind transcripts (vk_translation_step), editing the
+``ssa`` counts in place: transcripts, proteins and free ribosomes are species of that table.
+Division splits the pools with ``divide_split`` and deals the ribosomes out by a coin each
+(vk_divide_ribosomes).
+
 With a :class:`~lens_amd.cells.CellModel` the step continues like the
 reference's deriver pass: the growth process (from the step-start state),
 then TreeMass / DeriveGlobals (``mmol_to_counts`` for the next step's
@@ -103,6 +111,8 @@ from lens_amd.rate_law_compiler import compile_rate_laws, RateLawTable
 from lens_amd.response import CellResponse, ResponseBuffers, ResponseEngine
 from lens_amd.static_field import StaticField
 from lens_amd.stochastic import StochasticEngine, StochasticModel, describe_status, divide_counts, flagella_target
+from lens_amd.translation import (TranslationEngine, TranslationModel, describe_status as describe_tl_status,
+                                  divide_ribosomes, unpack as unpack_ribosome)
 
 
 def mmol_to_counts_from_mass(mass_fg, density_g_per_L=1100.0, avogadro=N_A_LEGACY):
@@ -140,10 +150,16 @@ AGENT_ARRAYS = (
 # a coin per (mother, species), and the key each agent draws by; daughters get fresh keys
 # (vk_divide_counts)
 STOCHASTIC_ARRAYS = (('ssa', 'counts'), ('ssa_key', 'counts'))
-_ALL_AGENT_ARRAYS = AGENT_ARRAYS + STOCHASTIC_ARRAYS
+# The per-agent arrays of Colony(translation=...): the ribosome list ([max_ribosomes][ld], one
+# packed word per ribosome, in insertion order) and its length, divided entry by entry with a
+# coin per (mother, entry) (vk_divide_ribosomes), and the monomers, ATP and ADP, split by
+# divide_split like the counts above (vk_divide_counts under a domain of its own)
+TRANSLATION_ARRAYS = (('ribosome_slots', 'ribosomes'), ('ribosome_count', 'ribosomes'), ('tl_molecules', 'molecules'))
+_ALL_AGENT_ARRAYS = AGENT_ARRAYS + STOCHASTIC_ARRAYS + TRANSLATION_ARRAYS
 # Tensors sized by the capacity that are not per-agent state: Colony._capacity_scratch
 # allocates them (the first row) or drops them for their users to allocate again (the second)
 CAPACITY_SCRATCH = ('bin_lin', 'bin_ix', 'env_bins', 'outflow', '_flag_expr_update', 'ssa_events', '_ssa_status',
+                    'tl_events', '_tl_status',
                     '_counts_alt', 'flux_steps', 'counts_steps', 'nsteps_steps', '_colony_shape')
 
 
@@ -155,6 +171,7 @@ class Colony:
     attempts = None          # count_attempts
     _flag_expression = _flag_flags = None        # FlagellaModel(expression=...) / (complexes=...)
     stochastic = _ssa = ssa = ssa_key = None     # Colony(stochastic=...)
+    translation = _tl = ribosome_slots = ribosome_count = tl_molecules = None    # Colony(translation=...)
     _x_stream = _p_stream = None                 # capture(overlap=True)
     _counts_alt = flux_steps = counts_steps = nsteps_steps = None    # capture(overlap=True), step_many
     _colony_shape = None                         # colony_metrics
@@ -166,7 +183,7 @@ class Colony:
                  table: Optional[RateLawTable] = None, specialize: bool = False,
                  cells: Optional[CellModel] = None, agent_ids=None, motility: Optional[MotilityModel] = None,
                  mechanics: Optional[ContactModel] = None, response: Optional[CellResponse] = None,
-                 stochastic: Optional[StochasticModel] = None):
+                 stochastic: Optional[StochasticModel] = None, translation: Optional[TranslationModel] = None):
         if integrator not in ('euler', 'dopri5'):
             raise ValueError('integrator must be euler or dopri5')
         if exchange not in ('sorted', 'atomic'):
@@ -218,6 +235,15 @@ class Colony:
                                  'saved and restored)')
             if complexes is not None:
                 stochastic.index(complexes)      # ValueError: the network has no such species
+        if translation is not None:
+            # checked before anything is built: the transcripts, the proteins and the free ribosome
+            # are species of the stochastic table, so every refusal above holds for translation too
+            if not isinstance(translation, TranslationModel):
+                raise ValueError('translation must be a TranslationModel')
+            if stochastic is None:
+                raise ValueError('translation needs a colony with stochastic=StochasticModel(...): its transcripts, '
+                                 'proteins and free ribosomes are species of that table')
+            translation.bind(stochastic)         # ValueError: the table lacks a species
         if mechanics is not None:
             # checked before anything is built, like motility: the contact launch moves and
             # re-bins the agents on the device, on one whole plane
@@ -324,6 +350,14 @@ class Colony:
             self.ssa = torch.from_numpy(stochastic.initial_counts(self.n, ld)).to(dev).contiguous()
             self.ssa_key = torch.arange(ld, dtype=torch.int64, device=dev)
             self._ssa_key_base = self.n
+        self.translation = translation
+        if translation is not None:
+            # the ribosome lists (empty), their lengths and the monomer pools (zero until
+            # set_translation_molecules); the draws go by ssa_key and the ssa engine's step word
+            self._tl = TranslationEngine(translation, stochastic, dev)
+            self.ribosome_slots = z(translation.max_ribosomes, ld, dtype=torch.int32)
+            self.ribosome_count = z(ld, dtype=torch.int32)
+            self.tl_molecules = z(len(translation.molecule_ids), ld, dtype=torch.int32)
         if response is not None:
             self.dead = z(ld, dtype=torch.int32)
             self.frozen = z(ld, dtype=torch.int32)
@@ -446,6 +480,9 @@ class Colony:
             # the events each agent fired in the last step; the status bits are sticky and
             # checked before the capacity changes (_regather), so nothing is lost here
             self.ssa_events, self._ssa_status = i32(), i32()
+        if getattr(self, 'translation', None) is not None:
+            # the initiations of the last step; the status bits are sticky like the ones above
+            self.tl_events, self._tl_status = i32(), i32()
         # sized by ld too, allocated by their users (capture(overlap=True), step_many, colony_metrics)
         self._counts_alt = self.flux_steps = self.counts_steps = self.nsteps_steps = None
         self._colony_shape = None
@@ -539,6 +576,49 @@ class Colony:
             if c.shape[0] < self.n:
                 raise ValueError('set_flagella: one count per agent (%d < %d)' % (c.shape[0], self.n))
             row.copy_(torch.from_numpy(c[:self.n].astype(np.int32)))
+
+    def _need_translation(self, what):
+        if self.translation is None:
+            raise ValueError('%s: a colony with translation=TranslationModel(...)' % what)
+
+    def ribosomes(self):
+        """Host copy of the ribosome lists: per agent a list of (template, position, occluding)
+        in insertion order; ``template`` indexes the model's ``transcript_order``."""
+        self._need_translation('ribosomes')
+        slots = self.ribosome_slots[:, :self.n].cpu().numpy()
+        count = self.ribosome_count[:self.n].cpu().numpy()
+        return [[unpack_ribosome(w) for w in slots[:count[a], a]] for a in range(self.n)]
+
+    def set_ribosomes(self, lists):
+        """The ribosome list of every agent [0, n): per agent a sequence of (template, position,
+        occluding).  Copied into the existing arrays, so a captured graph sees them at its next
+        replay.  A list longer than ``max_ribosomes`` or a ribosome outside its template raises."""
+        self._need_translation('set_ribosomes')
+        if len(lists) != self.n:
+            raise ValueError('set_ribosomes: one list per agent (%d != %d)' % (len(lists), self.n))
+        slots = np.zeros((self.translation.max_ribosomes, self.n), dtype=np.int32)
+        count = np.zeros(self.n, dtype=np.int32)
+        for a, ribosomes in enumerate(lists):
+            words = self.translation.check_ribosomes(list(ribosomes))
+            slots[:len(words), a], count[a] = words, len(words)
+        self.ribosome_slots[:, :self.n].copy_(torch.from_numpy(slots))
+        self.ribosome_count[:self.n].copy_(torch.from_numpy(count))
+
+    def set_translation_molecules(self, **counts):
+        """Monomer, ATP and ADP counts by name: an int for every agent or one value per agent
+        [0, n).  Copied into the existing ``tl_molecules`` rows."""
+        self._need_translation('set_translation_molecules')
+        ids = self.translation.molecule_ids
+        for name, value in counts.items():
+            if name not in ids:
+                raise ValueError('set_translation_molecules: no molecule %r (molecules: %s)' % (name, ids))
+            v = np.asarray(value)
+            if v.ndim and v.shape[0] < self.n:
+                raise ValueError('set_translation_molecules: one count per agent (%d < %d)' % (v.shape[0], self.n))
+            v = np.broadcast_to(v[:self.n] if v.ndim else v, (self.n,)).astype(np.int64)
+            if np.any(v < -2 ** 31) or np.any(v > 2 ** 31 - 1):
+                raise ValueError('set_translation_molecules: the count of %r does not fit int32' % (name,))
+            self.tl_molecules[ids.index(name), :self.n].copy_(torch.from_numpy(v.astype(np.int32)))
 
     def agent_array_names(self):
         """Every per-agent array this colony has (agent = column), as attribute names in
@@ -1155,6 +1235,8 @@ class Colony:
         if overlap and (self._counts_alt is None or self._counts_alt.shape != self.counts.shape):
             self._counts_alt = torch.zeros_like(self.counts)
         counts0 = self.counts
+        if self._tl is not None:
+            self._tl.plan(dt)                       # the sub-interval plan is uploaded before the capture
         graph = torch.cuda.CUDAGraph()
         t0, s0 = self.time, self.step_index
         layout, n = self._layout, self.n
@@ -1320,6 +1402,13 @@ class Colony:
             a = int(bad[0])
             raise FloatingPointError('agent %d: stochastic step status %d (%s)' % (
                 a, int(st[a]), describe_status(int(st[a]))))
+        if self._tl is not None:
+            st = self._tl_status[:self.n]
+            bad = torch.nonzero(st).flatten()
+            if bad.numel():
+                a = int(bad[0])
+                raise FloatingPointError('agent %d: translation step status %d (%s)' % (
+                    a, int(st[a]), describe_tl_status(int(st[a]))))
 
     def _finish_step(self, dt):
         if self._flag_expression is not None:
@@ -1328,6 +1417,14 @@ class Colony:
             # the mmol_to_counts the previous step left; both before vk_cell_step touches m2c
             self._flag_expression.step(dt, self.flag_expr, self.n, update=self._flag_expr_update, accumulate=True)
             self._flagella_counts()
+        if self._tl is not None:
+            # translation first, editing the ssa counts in place: the network below then sees the
+            # proteins this step completed (the sequential order is this engine's; the reference
+            # applies both processes' updates to the step-start state).  It draws under the step
+            # word the ssa launch advances, and under a domain of its own
+            self._tl.step(dt, self.ribosome_slots, self.ribosome_count, self.tl_molecules, self.ssa, self.ssa_key,
+                          self.n, events=self.tl_events, status=self._tl_status,
+                          step_counter=self._ssa.step_counter, advance=False)
         if self._ssa is not None:
             # the stochastic network over the step, every agent on her own clock and by her own
             # key; then the flagella count the NEXT step's motor reads (the reference's
@@ -1543,6 +1640,18 @@ class Colony:
                 new['ssa'], new['ssa_key'] = empty(old['ssa']), empty(old['ssa_key'])
                 divide_counts(n_out, n_out - n_daughters, n, src, kind, old['ssa'], old['ssa_key'], new['ssa'],
                               new['ssa_key'], self.stochastic.seed, self.step_index, self._ssa_key_base)
+                if 'ribosome_slots' in old:
+                    # the list entry by entry and the pools by divide_split, both keyed by the
+                    # mothers' keys (the old ssa_key) under domains of their own
+                    tm = self.translation
+                    for name in ('ribosome_slots', 'ribosome_count', 'tl_molecules'):
+                        new[name] = empty(old[name])
+                    divide_ribosomes(n_out, n, src, kind, old['ribosome_slots'], old['ribosome_count'],
+                                     old['ssa_key'], new['ribosome_slots'], new['ribosome_count'], tm.seed,
+                                     self.step_index)
+                    divide_counts(n_out, n_out - n_daughters, n, src, kind, old['tl_molecules'], old['ssa_key'],
+                                  new['tl_molecules'], torch.empty_like(new['ssa_key']),
+                                  tm.seed ^ native.VK_TL_DIVIDE_DOMAIN, self.step_index, self._ssa_key_base)
                 self._ssa_key_base += n_daughters
         for name, t in new.items():
             setattr(self, name, t)
@@ -1628,4 +1737,10 @@ class Colony:
             out['stochastic'] = {name: x[row].copy() for row, name in enumerate(self.stochastic.species)}
             out['ssa_key'] = self.ssa_key[:self.n].cpu().numpy().copy()
             out['ssa_events'] = self.ssa_events[:self.n].cpu().numpy().copy()
+        if self.translation is not None:
+            m = self.tl_molecules[:, :self.n].cpu().numpy()
+            out['translation_molecules'] = {name: m[row].copy() for row, name in
+                                            enumerate(self.translation.molecule_ids)}
+            out['ribosome_count'] = self.ribosome_count[:self.n].cpu().numpy().copy()
+            out['translation_events'] = self.tl_events[:self.n].cpu().numpy().copy()
         return out

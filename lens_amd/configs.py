@@ -344,5 +344,48 @@ def chemotaxis_ode_expression_flagella(expression=None, division='merged', **mot
             'motility': MotilityModel(flagella=flagella, division=division, **motility)}
 
 
+AMINO_ACIDS = {
+    'A': 'Alanine', 'R': 'Arginine', 'N': 'Asparagine', 'D': 'Aspartate', 'C': 'Cysteine', 'E': 'Glutamate',
+    'Q': 'Glutamine', 'G': 'Glycine', 'H': 'Histidine', 'I': 'Isoleucine', 'L': 'Leucine', 'K': 'Lysine',
+    'M': 'Methionine', 'F': 'Phenylalanine', 'P': 'Proline', 'S': 'Serine', 'T': 'Threonine', 'W': 'Tryptophan',
+    'Y': 'Tyrosine', 'V': 'Valine'}
+
+
+def flagella_translation(data, operons=None, sequences=None, seed=SEED, **model):
+    """The translation process of the reference's flagella agent
+    (vivarium/compartments/flagella_expression.py:110-117) as a
+    :class:`~lens_amd.translation.TranslationModel`, from a dict of the shape of
+    tests/golden/flagella_translation.json: ``transcripts`` [(operon, product)],
+    ``transcript_affinities`` (one per transcript), ``elongation_rate``,
+    ``polymerase_occlusion`` and ``sequences`` ({product: 'MSK...'}) or, where the real ones
+    are not at hand, ``estimated_length`` ({product: residues}), from which seeded uniform
+    random sequences over the 20 amino acids are drawn -- the size and the shape of the
+    reference's model, not its proteins.  ``operons`` keeps only those operons' transcripts:
+    the whole chromosome has 15 operons and 49 products, one species more than the 64 a
+    StochasticModel holds beside the free ribosome.  Templates are the reference's
+    generate_template: one terminator at the sequence's end, the product its only product.
+    An operon's transcript is the species ``<operon>_RNA`` of the stochastic table.
+    Further keyword arguments (``max_ribosomes``, ``release``, ``seed`` of the draws, ...)
+    go to the TranslationModel."""
+    from lens_amd.translation import TranslationModel
+    sequences = sequences if sequences is not None else data.get('sequences')
+    rng = np.random.default_rng(seed)
+    symbols = sorted(AMINO_ACIDS)
+    if sequences is None:
+        sequences = {p: ''.join(symbols[i] for i in rng.integers(0, len(symbols), int(length)))
+                     for p, length in sorted(data['estimated_length'].items())}
+    keys = [(o, p) for o, p in map(tuple, data['transcripts']) if operons is None or o in operons]
+    affinity = {tuple(k): a for k, a in zip(data['transcripts'], data['transcript_affinities'])}
+    templates = {k: {'id': k, 'position': 0, 'direction': 1, 'sites': [], 'terminators': [
+        {'position': len(sequences[k[1]]), 'strength': 1.0, 'products': [k[1]]}]} for k in keys}
+    model.setdefault('seed', seed)
+    # the reference keeps transcripts and proteins in two stores; in one table the operon fliL
+    # and the protein fliL need two names
+    model.setdefault('transcript_species', {o: o + '_RNA' for o, _ in keys})
+    return TranslationModel({k: sequences[k[1]] for k in keys}, templates, {k: affinity[k] for k in keys},
+                            data['elongation_rate'], data['polymerase_occlusion'], AMINO_ACIDS,
+                            list(AMINO_ACIDS.values()), **model)
+
+
 def deepcopy_config(cfg):
     return copy.deepcopy(cfg)

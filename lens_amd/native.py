@@ -39,6 +39,7 @@ EXPORTS = (
     'vk_ssa_step', 'vk_ssa_propensities', 'vk_divide_counts', 'vk_ssa_flagella_target',
     'vk_colonies_scratch_bytes', 'vk_colony_metrics',
     'vk_gradient_fill', 'vk_static_gather', 'vk_motility_step_static', 'vk_flagella_step_static',
+    'vk_translation_step', 'vk_divide_ribosomes',
 )
 
 VK_CELL_MASS, VK_CELL_VOLUME, VK_CELL_LENGTH, VK_CELL_SURFACE_AREA, VK_CELL_PROTEIN, VK_CELL_ANGLE = range(6)
@@ -56,6 +57,11 @@ VK_SSA_MAX_SPECIES, VK_SSA_MAX_REACTIONS, VK_SSA_MAX_ORDER = 64, 32, 255
 VK_SSA_DOMAIN = 0x7373615f73746570                 # mixed into the seed of vk_ssa_step's draws
 VK_SSA_DIVIDE_DOMAIN = 0x7373615f64697669          # and of vk_divide_counts' coins
 VK_SSA_MAX_EVENTS, VK_SSA_NONFINITE, VK_SSA_OVERFLOW, VK_SSA_BAD_KEY = 1, 2, 4, 8
+VK_TL_MAX_SLOTS, VK_TL_MAX_TEMPLATES, VK_TL_MAX_MONOMERS, VK_TL_MAX_POSITION = 128, 64, 24, 0x00ffffff
+VK_TL_DOMAIN = 0x746c5f5f73746570                  # mixed into the seed of vk_translation_step's draws
+VK_TL_DIVIDE_DOMAIN = 0x746c5f5f64697669           # and of vk_divide_ribosomes' coins
+VK_TL_SLOTS_FULL, VK_TL_BAD_KEY, VK_TL_NONFINITE, VK_TL_OVERFLOW, VK_TL_MAX_EVENTS = 1, 2, 4, 8, 16
+VK_TL_RELEASE_REFERENCE, VK_TL_RELEASE_TEMPLATE = 0, 1
 (VK_COLONY_MASS, VK_COLONY_CELL_AREA, VK_COLONY_CX, VK_COLONY_CY, VK_COLONY_SXX, VK_COLONY_SYY, VK_COLONY_SXY,
  VK_COLONY_ANGLE, VK_COLONY_MAJOR, VK_COLONY_MINOR) = range(10)
 VK_COLONY_ROWS = 10
@@ -161,6 +167,13 @@ class VkSsaNet(ctypes.Structure):
                            'stoich_delta', 'rates', 'inv')]
 
 
+class VkTlModel(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('n_templates', 'n_monomers', 'n_species', 'max_slots', 'occlusion',
+                                              'release', 'ribosome_species', 'n_plan')] + [
+        (n, _vp) for n in ('operon_species', 'seq_ptr', 'prod_ptr', 'prod_species', 'elongate', 'seq', 'affinity',
+                           'interval')]
+
+
 class VkPass(ctypes.Structure):
     """One pass of a diffusion call's plan (vk_diffuse_plan)."""
     _fields_ = [(n, ctypes.c_int32) for n in ('k', 'src', 'dst', 'f0', 'lo', 'hi', 'in_lo', 'in_hi', 'gap_lo',
@@ -237,6 +250,10 @@ _SIGS = {
     'vk_divide_counts': ([_i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i32, ctypes.c_uint64,
                           ctypes.c_uint64, _i64, _vp], ctypes.c_int),
     'vk_ssa_flagella_target': ([_i64, _vp, _vp, _vp, _vp], ctypes.c_int),
+    'vk_translation_step': ([ctypes.POINTER(VkTlModel), _i64, _i64, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, _vp,
+                             _i32, _i32, _vp, _vp, _vp], ctypes.c_int),
+    'vk_divide_ribosomes': ([_i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, ctypes.c_uint64,
+                             ctypes.c_uint64, _vp], ctypes.c_int),
     'vk_occupancy_scratch_bytes': ([_i64], ctypes.c_int64),
     'vk_occupancy_sort': ([_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp], ctypes.c_int),
     'vk_exchange_ordered': ([_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _f64, _vp], ctypes.c_int),
