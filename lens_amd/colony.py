@@ -87,11 +87,18 @@ reference's deriver pass: the growth process (from the step-start state),
 then TreeMass / DeriveGlobals (``mmol_to_counts`` for the next step's
 exchange), then division: survivors keep their order, daughters are appended
 in mother order, every per-agent array is gathered once with its divider.
+
+Which agents the colony holds, in what order and at what capacity changes in one place,
+lens_amd/population.py: division, removal and the mother machine's outflow take one plan
+(``plan_population``) and gather by the table of per-agent arrays (``regather``); they,
+:meth:`Colony.sort_by_bin` and the router's migration end in one ``install``, which reads the
+sticky status words before the columns move and always moves ``_layout``.
 """
 
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 from typing import Optional
 
 import numpy as np
@@ -105,14 +112,16 @@ from lens_amd.expression import ExpressionEngine
 from lens_amd.kinetics import KineticsEngine
 from lens_amd.lattice import Lattice, occupancy, segment_index, whole_plane, N_A_LEGACY
 from lens_amd.mechanics import ContactBuffers, ContactModel, contact_step
-from lens_amd.motility import (DeviceOccupancy, DIVISION_MODES, MotilityModel, ROW_NAMES as MOTIL_ROW_NAMES, FLAG_ROW_NAMES,
+from lens_amd.motility import (DeviceOccupancy, MotilityModel, ROW_NAMES as MOTIL_ROW_NAMES, FLAG_ROW_NAMES,
                                FLAGI_ROW_NAMES, check_flagella_counts, flagella_step, motility_step)
+# the table of per-agent arrays and everything that re-lays a colony out (lens_amd/population.py)
+from lens_amd.population import AGENT_ARRAYS, _ALL_AGENT_ARRAYS, install, plan_population, regather
 from lens_amd.rate_law_compiler import compile_rate_laws, RateLawTable
 from lens_amd.response import CellResponse, ResponseBuffers, ResponseEngine
 from lens_amd.static_field import StaticField
-from lens_amd.stochastic import StochasticEngine, StochasticModel, describe_status, divide_counts, flagella_target
+from lens_amd.stochastic import StochasticEngine, StochasticModel, describe_status, flagella_target
 from lens_amd.translation import (TranslationEngine, TranslationModel, describe_status as describe_tl_status,
-                                  divide_ribosomes, unpack as unpack_ribosome)
+                                  unpack as unpack_ribosome)
 
 
 def mmol_to_counts_from_mass(mass_fg, density_g_per_L=1100.0, avogadro=N_A_LEGACY):
@@ -120,42 +129,6 @@ def mmol_to_counts_from_mass(mass_fg, density_g_per_L=1100.0, avogadro=N_A_LEGAC
     return avogadro * (mass_fg / density_g_per_L * 1e-15) * 1e-3
 
 
-_SET, _SPLIT, _ZERO = native.VK_DIVIDE_SET, native.VK_DIVIDE_SPLIT, native.VK_DIVIDE_ZERO
-
-# Every per-agent array (agent = column; the last dimension is the capacity ``ld``), in the
-# order agent_array_names() reports, with its divider: what each daughter gets of the
-# mother's value.  A vk_divide_gather mode, or row ranges (lo, hi, mode) of one, or the name
-# of a divider with a launch of its own (Colony._regather).  A colony has an array if and
-# only if the attribute is a tensor.  A new per-agent array is one row here.
-AGENT_ARRAYS = (
-    ('params', _SET), ('conc', _SET), ('m2c', _SET), ('flux', _SET), ('counts', _SET), ('status', _SET),
-    ('nsteps', _SET), ('h_state', _SET),
-    ('location', 'locations'),           # daughters along the mother's angle (vk_divide_locations)
-    ('cell', ((0, native.VK_CELL_ANGLE, _SPLIT), (native.VK_CELL_ANGLE, native.VK_CELL_ROWS, _SET))),
-    ('divide', _ZERO),
-    ('lin_root', 'lineage'), ('lin_depth', 'lineage'), ('lin_path', 'lineage'),      # vk_divide_lineage
-    # 'dead' has no divider in the reference (both daughters inherit it); the daughters'
-    # processes are generated anew, so they are not frozen
-    ('dead', _SET), ('frozen', _ZERO),
-    # the receptor's and the motor's scalars, PMF and the expression's concentrations have
-    # no divider either.  The flagella count is split, the flagella go by the model's
-    # ``division`` mode, daughters get fresh keys (vk_divide_flagella)
-    ('motil', _SET), ('flag', _SET), ('flag_int', 'flagella'), ('flag_expr', _SET), ('motile_key', 'flagella'),
-    ('mech_angle', _SET),
-    ('ordinal', 'given'),                # the router's global order, computed by a collective
-    ('env_fields', _SET),                # NonSpatialEnvironment: each agent's own 1x1 field
-)
-# The per-agent arrays of Colony(stochastic=...), two more rows of the same table, reported
-# after the ones above: the int counts of the stochastic network, split by divide_split with
-# a coin per (mother, species), and the key each agent draws by; daughters get fresh keys
-# (vk_divide_counts)
-STOCHASTIC_ARRAYS = (('ssa', 'counts'), ('ssa_key', 'counts'))
-# The per-agent arrays of Colony(translation=...): the ribosome list ([max_ribosomes][ld], one
-# packed word per ribosome, in insertion order) and its length, divided entry by entry with a
-# coin per (mother, entry) (vk_divide_ribosomes), and the monomers, ATP and ADP, split by
-# divide_split like the counts above (vk_divide_counts under a domain of its own)
-TRANSLATION_ARRAYS = (('ribosome_slots', 'ribosomes'), ('ribosome_count', 'ribosomes'), ('tl_molecules', 'molecules'))
-_ALL_AGENT_ARRAYS = AGENT_ARRAYS + STOCHASTIC_ARRAYS + TRANSLATION_ARRAYS
 # Tensors sized by the capacity that are not per-agent state: Colony._capacity_scratch
 # allocates them (the first row) or drops them for their users to allocate again (the second)
 CAPACITY_SCRATCH = ('bin_lin', 'bin_ix', 'env_bins', 'outflow', '_flag_expr_update', 'ssa_events', '_ssa_status',
@@ -375,7 +348,6 @@ class Colony:
             self.lin_root = torch.arange(ld, dtype=torch.int32, device=dev)
             self.lin_depth = z(ld, dtype=torch.int32)
             self.lin_path = z(ld, dtype=torch.int64)
-            self._n_out = torch.zeros(1, dtype=torch.int64, device=dev)
             self._overflow = torch.zeros(1, dtype=torch.int32, device=dev)
         self.environment = environment
         if isinstance(environment, (Lattice, StaticField)):
@@ -446,8 +418,8 @@ class Colony:
     def _capacity_scratch(self):
         """Everything sized by the capacity that is not per-agent state (CAPACITY_SCRATCH and
         the buffer objects), for the current ``ld``: the only place that allocates it.  Called
-        by the constructor and whenever ``ld`` changes, by division or by
-        distributed.install_agents; captured graphs hold the old buffers, so ``_layout`` moves."""
+        by the constructor and by population.install whenever ``ld`` changes; captured graphs
+        hold the old buffers, so ``_layout`` moves."""
         ld, dev, lat = self.ld, self.device, self.lattice
         i32 = lambda: torch.zeros(ld, dtype=torch.int32, device=dev)
         if lat is not None or getattr(self, 'static', None) is not None:   # a borrowed hook: see stochastic below
@@ -478,7 +450,7 @@ class Colony:
                                                  dtype=torch.float64, device=dev)
         if getattr(self, 'stochastic', None) is not None:       # objects that only borrow this hook lack it
             # the events each agent fired in the last step; the status bits are sticky and
-            # checked before the capacity changes (_regather), so nothing is lost here
+            # checked before the capacity changes (population.install), so nothing is lost here
             self.ssa_events, self._ssa_status = i32(), i32()
         if getattr(self, 'translation', None) is not None:
             # the initiations of the last step; the status bits are sticky like the ones above
@@ -700,18 +672,12 @@ class Colony:
         key = prev if prev is not None else torch.arange(n, dtype=torch.int64, device=self.device)
         by_key = torch.sort(key[:n], stable=True).indices
         perm = by_key[torch.sort(self.bin_lin[:n].to(torch.int64)[by_key], stable=True).indices]
-        for name in self.agent_array_names() + ['bin_lin', 'bin_ix']:
-            t = getattr(self, name)
-            if t.dim() == 1:
-                t[:n] = t[:n][perm]
-            else:
-                t[:, :n] = t[:, :n][:, perm]
-        self.agent_order = key[perm]
-        self.occ = occupancy(self.bin_lin, n, self.agent_order)
-        if self.response is not None and self.exchange_mode == 'sorted':
-            self._occ_dev.sort(self.bin_lin, n, self.lattice.rows_local * self.lattice.ny, self.agent_order)
-        self._update_coupling()
-        self._layout += 1            # captured graphs hold the old occupancy buffers
+        # every column of the capacity: the permuted agents, then the unused ones as they are
+        columns = torch.cat([perm, torch.arange(n, self.ld, device=self.device)])
+        new = {name: getattr(self, name).index_select(-1, columns) for name in self.agent_array_names()}
+        new['agent_order'] = key[perm]
+        install(self, new, n)
+        self.refresh_bins()          # the bins are a function of the location: the same values, permuted
         return self.agent_order
 
     def _gather_fused(self):
@@ -1459,9 +1425,6 @@ class Colony:
         cm, n = self.cells, self.n
         if n == 0 and self.router is None:
             return 0
-        src = torch.empty(2 * n, dtype=torch.int32, device=self.device)
-        kind = torch.empty(2 * n, dtype=torch.int32, device=self.device)
-        n_out = 0
         if n:
             p = cm.vk_params(dt, self.step_index)
             u = None
@@ -1476,47 +1439,28 @@ class Colony:
                 native.ptr(self.divide), native.stream_handle()), 'vk_cell_step')
             if self.response is not None:
                 self._resp.cells(True, n, self.frozen, self.cell, self.m2c, self.divide, self._resp_buf)
-            if self._channels():
-                # the mother machine: the agents the contact launch flagged leave with this
-                # plan, and a flagged mother leaves no daughters.  Still one host read: the new
-                # count and the number removed together (equal counts can hide a removal)
-                scratch = torch.empty(int(native._lib.vk_population_scratch_bytes(n)), dtype=torch.uint8,
-                                      device=self.device)
-                native.check(native._lib.vk_population_plan(
-                    native.ptr(self.divide), native.ptr(self.outflow), n, native.ptr(src), native.ptr(kind),
-                    native.ptr(self._n_out), native.ptr(scratch), native.stream_handle()), 'vk_population_plan')
-                n_out, n_removed = torch.stack([self._n_out[0], (self.outflow[:n] != 0).sum()]).tolist()
-                self._mech.check()       # the too-long flag, where the host reads anyway
-                if n_out == n and n_removed == 0:
-                    return 0
-                self._apply_division(n_out, src, kind)
-                return n_out - n + n_removed
-            scratch = torch.empty(int(native._lib.vk_divide_scratch_bytes(n)), dtype=torch.uint8,
-                                  device=self.device)
-            native.check(native._lib.vk_divide_plan(
-                native.ptr(self.divide), n, native.ptr(src), native.ptr(kind), native.ptr(self._n_out),
-                native.ptr(scratch), native.stream_handle()), 'vk_divide_plan')
-            n_out = int(self._n_out.item())
-            if self.mechanics is not None:
-                self._mech.check()       # the too-long flag, where the host reads anyway
-            if self.motility is not None:
-                self._flagella_check()   # the count flag, where the host reads anyway
+        # the mother machine: the agents the contact launch flagged leave with this plan, and a
+        # flagged mother leaves no daughters.  One host read either way; the flags the host
+        # checks ride on it (the contact launch's too-long flag, the flagella count flag)
+        plan = plan_population(n, self.divide, self.outflow if self._channels() else None, self.device)
+        if n and self.mechanics is not None:
+            self._mech.check()
+        if n and self.motility is not None:
+            self._flagella_check()
         if self.router is not None:
-            # collective every step: the global order of every rank's survivors
-            # and daughters (AgentRouter.division_ordinals); then, if any rank
+            # collective every step, also with no agents: the global order of every rank's
+            # survivors and daughters (AgentRouter.division_ordinals); then, if any rank
             # divided, daughters that left this band move to their owner
-            new_ord, n_div = self.router.division_ordinals(self.ordinal[:n], self.divide[:n] != 0, src, kind,
-                                                           n_out)
-            if n_out != n:
-                self._apply_division(n_out, src, kind, ordinal=new_ord)
+            new_ord, n_div = self.router.division_ordinals(self.ordinal[:n], self.divide[:n] != 0, plan.src,
+                                                           plan.kind, plan.n_out)
+            if plan.n_out != n:
+                regather(self, dataclasses.replace(plan, ordinal=new_ord))
             elif n_div:
                 self.ordinal[:n] = new_ord
                 self.refresh_bins()
-            return n_out - n
-        if n_out == n:
-            return 0
-        self._apply_division(n_out, src, kind)
-        return n_out - n
+        elif plan.n_out != n or plan.n_removed:
+            regather(self, plan)
+        return plan.n_daughters // 2
 
     def _channels(self):
         """Whether this colony is a mother machine (mechanics with channels)."""
@@ -1533,138 +1477,14 @@ class Colony:
         if self.router is not None or (lat is not None and not whole_plane(lat)):
             raise ValueError('Colony.remove: a colony with a router or a banded lattice keeps its agents '
                              '(their global order lives on other ranks)')
-        n, ld, dev, st = self.n, self.ld, self.device, native.stream_handle()
+        n, dev = self.n, self.device
         if not torch.is_tensor(mask) or mask.device.type != dev.type or mask.dim() != 1 or mask.shape[0] < n or \
                 mask.dtype not in (torch.int32, torch.bool):
             raise ValueError('Colony.remove: mask must be a device int32 or bool tensor over agents [0, n)')
-        if n == 0:
-            return 0
-        flags = mask[:n].to(torch.int32).contiguous()
-        src = torch.empty(n, dtype=torch.int32, device=dev)
-        kind = torch.empty(n, dtype=torch.int32, device=dev)
-        n_out_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-        scratch = torch.empty(int(native._lib.vk_population_scratch_bytes(n)), dtype=torch.uint8, device=dev)
-        native.check(native._lib.vk_population_plan(
-            0, native.ptr(flags), n, native.ptr(src), native.ptr(kind), native.ptr(n_out_dev), native.ptr(scratch),
-            st), 'vk_population_plan')
-        n_out = int(n_out_dev.item())
-        if n_out == n:
-            return 0
-        self._regather(n_out, src, kind, ld, declared=False)
-        return n - n_out
-
-    def _apply_division(self, n_out, src, kind, ordinal=None):
-        if self.motility is not None and self._key_base + 2 * (n_out - self.n) - 1 > 2 ** 31 - 1:
-            # before any array is gathered into the new layout
-            raise OverflowError('a motility key would pass 2**31 - 1 (the kernels put it into a 32-bit counter word)')
-        if self.stochastic is not None and self._ssa_key_base + n_out - 1 > 2 ** 31 - 1:
-            # at most n_out daughters
-            raise OverflowError('a stochastic key would pass 2**31 - 1 (the kernel puts it into a 32-bit counter word)')
-        ld = self.ld if n_out <= self.ld else max(n_out, int(self.ld * 1.25) + 64)
-        self._regather(n_out, src, kind, ld, ordinal=ordinal)
-        if int(self._overflow.item()):
-            raise OverflowError('a lineage exceeded 64 generations (phylogeny path bits)')
-
-    def _regather(self, n_out, src, kind, ld, declared=True, ordinal=None):
-        """Every per-agent array gathered once by a plan (``src`` / ``kind`` of vk_divide_plan
-        or vk_population_plan, ``n_out`` agents) into capacity ``ld``: each with the divider
-        AGENT_ARRAYS declares into uninitialised arrays (division), or, ``declared=False``,
-        all with the set divider into zero-filled ones (removal: the plan holds no daughters;
-        ``agent_order`` is compacted to its ``n_out`` keys).  Only the old arrays are read;
-        the new ones are installed together, then the scratch follows the capacity and the
-        bins and occupancies are rebuilt."""
-        dev, st, n, ld_src = self.device, native.stream_handle(), self.n, self.ld
-        self._ssa_check()                    # the status bits go by column: read before the columns move
-        alloc = torch.empty if declared else torch.zeros
-        plan = (n_out, native.ptr(src), native.ptr(kind))
-        new = {}
-
-        def gather(name, t, ld_dst, ranges):
-            t = t.contiguous()               # flux / counts / nsteps may view step_many's buffers
-            out = alloc(t.shape[:-1] + (ld_dst,), dtype=t.dtype, device=dev)
-            size, ld_t = t.element_size(), t.shape[-1]
-            for lo, hi, mode in ranges:
-                rows = 1 if t.dim() == 1 else (t.shape[0] if hi is None else hi) - lo
-                native.check(native._lib.vk_divide_gather(
-                    *plan, t.data_ptr() + lo * ld_t * size, ld_t, out.data_ptr() + lo * ld_dst * size, ld_dst, rows,
-                    size, mode, st), 'vk_divide_gather(%s)' % name)
-            return out
-
-        old = {name: getattr(self, name) for name in self.agent_array_names()}
-        for name, divider in _ALL_AGENT_ARRAYS:
-            if name not in old:
-                continue
-            if not declared:
-                divider = _SET
-            if isinstance(divider, int):
-                divider = ((0, None, divider),)          # every row
-            if isinstance(divider, tuple):
-                new[name] = gather(name, old[name], ld, divider)
-            elif divider == 'given':
-                new[name] = torch.zeros(ld, dtype=torch.int64, device=dev)
-                new[name][:n_out] = ordinal
-        if not declared and self.agent_order is not None:
-            new['agent_order'] = gather('agent_order', self.agent_order, n_out, ((0, None, _SET),))
-        if declared:
-            # the dividers with a launch of their own: each writes several arrays, or reads a gathered one
-            empty = lambda like: torch.empty(like.shape[:-1] + (ld,), dtype=like.dtype, device=dev)
-            lineage = [old[name] for name in ('lin_root', 'lin_depth', 'lin_path')]
-            new.update({name: empty(old[name]) for name in ('lin_root', 'lin_depth', 'lin_path')})
-            native.check(native._lib.vk_divide_lineage(
-                *plan, *map(native.ptr, lineage), native.ptr(new['lin_root']), native.ptr(new['lin_depth']),
-                native.ptr(new['lin_path']), native.ptr(self._overflow), st), 'vk_divide_lineage')
-            if 'location' in old:
-                # along the mother's angle, by a quarter of the length she had: the gathered cell rows
-                new['location'] = empty(old['location'])
-                native.check(native._lib.vk_divide_locations(
-                    *plan, native.ptr(old['location']), ld_src, native.ptr(new['location']), ld,
-                    native.ptr(new['cell']), st), 'vk_divide_locations')
-            if 'motile_key' in old:
-                # the split's draw is keyed by the mother's lineage; a colony on the coarse motor
-                # has no flagella and gets keys only
-                m, n_daughters = self.motility, 2 * (n_out - n)      # vk_divide_plan: nobody is removed
-                new['motile_key'] = empty(old['motile_key'])
-                if 'flag_int' in old:
-                    new['flag_int'] = empty(old['flag_int'])
-                native.check(native._lib.vk_divide_flagella(
-                    n_out, n_out - n_daughters, n, native.ptr(src), native.ptr(kind), native.ptr(old.get('flag_int')),
-                    ld_src, native.ptr(old['motile_key']), *map(native.ptr, lineage), native.ptr(new.get('flag_int')),
-                    ld, native.ptr(new['motile_key']), DIVISION_MODES[m.division], m.seed & (2 ** 64 - 1),
-                    self.step_index & (2 ** 64 - 1), self._key_base, st), 'vk_divide_flagella')
-                self._key_base += n_daughters
-            if 'ssa' in old:
-                # divide_split on every species, a coin per (mother, species) keyed by the
-                # mother's key.  The plan may hold removed agents (vk_population_plan), so the
-                # daughters are counted: one more host read where the host reads anyway
-                n_daughters = int((kind[:n_out] >= 0).sum())
-                new['ssa'], new['ssa_key'] = empty(old['ssa']), empty(old['ssa_key'])
-                divide_counts(n_out, n_out - n_daughters, n, src, kind, old['ssa'], old['ssa_key'], new['ssa'],
-                              new['ssa_key'], self.stochastic.seed, self.step_index, self._ssa_key_base)
-                if 'ribosome_slots' in old:
-                    # the list entry by entry and the pools by divide_split, both keyed by the
-                    # mothers' keys (the old ssa_key) under domains of their own
-                    tm = self.translation
-                    for name in ('ribosome_slots', 'ribosome_count', 'tl_molecules'):
-                        new[name] = empty(old[name])
-                    divide_ribosomes(n_out, n, src, kind, old['ribosome_slots'], old['ribosome_count'],
-                                     old['ssa_key'], new['ribosome_slots'], new['ribosome_count'], tm.seed,
-                                     self.step_index)
-                    divide_counts(n_out, n_out - n_daughters, n, src, kind, old['tl_molecules'], old['ssa_key'],
-                                  new['tl_molecules'], torch.empty_like(new['ssa_key']),
-                                  tm.seed ^ native.VK_TL_DIVIDE_DOMAIN, self.step_index, self._ssa_key_base)
-                self._ssa_key_base += n_daughters
-        for name, t in new.items():
-            setattr(self, name, t)
-        self.n = n_out
-        if ld != self.ld:
-            self.ld = ld
-            self._capacity_scratch()
-        if declared and 'ssa' in old and self._ssa_complex() is not None:
-            self._ssa_flagella()         # the daughters' motors read their own share of the complex
-        if self.lattice is not None:
-            self.refresh_bins()          # bins, host and device occupancy, the _layout bump
-        else:
-            self._layout += 1
+        plan = plan_population(n, None, mask[:n].to(torch.int32).contiguous(), dev)
+        if plan.n_removed:
+            regather(self, plan, declared=False)
+        return plan.n_removed
 
     def agent_ids(self):
         """Phylogeny ids of agents 0..n-1 (meta_division.py:15-18)."""

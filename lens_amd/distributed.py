@@ -17,6 +17,8 @@ from typing import List, Tuple
 import torch
 import torch.distributed as dist
 
+from lens_amd.population import grown_capacity, install
+
 
 def row_bands(nx: int, world: int) -> List[Tuple[int, int]]:
     """Near-equal contiguous row bands [lo, hi) for each rank."""
@@ -295,22 +297,16 @@ def unpack_agents(col, names, recv):
 
 
 def install_agents(col, names, pieces):
-    """Replace every per-agent array by ``pieces[name]`` ([rows, n_new]),
-    growing the capacity when needed (the colony's scratch then follows it)."""
+    """Replace every per-agent array by ``pieces[name]`` ([rows, n_new]) padded with zeros
+    to the capacity, grown when needed (population.install: the colony's scratch follows it)."""
     n_new = pieces[names[0]].shape[1]
-    ld = col.ld if n_new <= col.ld else max(n_new, int(col.ld * 1.25) + 64)
+    ld = grown_capacity(col.ld, n_new)
+    arrays = {}
     for name in names:
         t = getattr(col, name)
-        out = torch.zeros((ld,) if t.dim() == 1 else (t.shape[0], ld), dtype=t.dtype, device=col.device)
-        if t.dim() == 1:
-            out[:n_new] = pieces[name].reshape(-1)
-        else:
-            out[:, :n_new] = pieces[name]
-        setattr(col, name, out)
-    col.n = n_new
-    if ld != col.ld:
-        col.ld = ld
-        col._capacity_scratch()
+        arrays[name] = torch.zeros(t.shape[:-1] + (ld,), dtype=t.dtype, device=col.device)
+        arrays[name][..., :n_new] = pieces[name].reshape(t.shape[:-1] + (n_new,))
+    install(col, arrays, n_new)
 
 
 class AgentBalancer:

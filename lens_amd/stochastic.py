@@ -232,6 +232,24 @@ def divide_counts(n_out, n_keep, n_src, src, kind, counts_src, key_src, counts_d
         native.stream_handle()), 'vk_divide_counts')
 
 
+def divide_agent_counts(col, plan, old, new, ld):
+    """The colony's divider of ``ssa`` / ``ssa_key`` (population.DIVIDERS): divide_split on every
+    species, a coin per (mother, species) keyed by the mother's key; daughters get the keys from
+    the colony's base on.  Once installed: the base moves past them, and the daughters' motors
+    read their own share of the flagella complex."""
+    base = col._ssa_key_base
+    if base + plan.n_daughters - 1 > 2 ** 31 - 1:
+        raise OverflowError('a stochastic key would pass 2**31 - 1 (the kernel puts it into a 32-bit counter word)')
+    divide_counts(plan.n_out, plan.n_keep, plan.n_src, plan.src, plan.kind, old['ssa'], old['ssa_key'], new['ssa'],
+                  new['ssa_key'], col.stochastic.seed, col.step_index, base)
+
+    def installed(col):
+        col._ssa_key_base = base + plan.n_daughters
+        if col._ssa_complex() is not None:
+            col._ssa_flagella()
+    return installed
+
+
 def flagella_target(n, counts_row, target, flags):
     """vk_ssa_flagella_target on the current stream: ``target[:n] = clamp(counts_row[:n], 0, 32)``;
     ``counts_row`` / ``target``: int32 device rows (views), ``flags``: one device int32."""

@@ -24,7 +24,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from lens_amd import native
-from lens_amd.stochastic import StochasticModel, _whole
+from lens_amd.stochastic import StochasticModel, _whole, divide_counts
 
 MAX_SLOTS, MAX_TEMPLATES, MAX_MONOMERS = native.VK_TL_MAX_SLOTS, native.VK_TL_MAX_TEMPLATES, native.VK_TL_MAX_MONOMERS
 UNBOUND_RIBOSOME_KEY = 'Ribosome'
@@ -306,3 +306,20 @@ def divide_ribosomes(n_out, n_src, src, kind, slots_src, length_src, key_src, sl
         slots_src.shape[-1], native.ptr(key_src), native.ptr(slots_dst), native.ptr(length_dst), slots_dst.shape[-1],
         slots_src.shape[0], int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), native.stream_handle()),
         'vk_divide_ribosomes')
+
+
+def divide_agent_ribosomes(col, plan, old, new, ld):
+    """The colony's divider of ``ribosome_slots`` / ``ribosome_count`` (population.DIVIDERS): the
+    list entry by entry, a coin per (mother, entry) keyed by the mother's key (the old ``ssa_key``)."""
+    divide_ribosomes(plan.n_out, plan.n_src, plan.src, plan.kind, old['ribosome_slots'], old['ribosome_count'],
+                     old['ssa_key'], new['ribosome_slots'], new['ribosome_count'], col.translation.seed,
+                     col.step_index)
+
+
+def divide_agent_molecules(col, plan, old, new, ld):
+    """The colony's divider of ``tl_molecules``: divide_split like the stochastic counts, by the
+    mothers' keys under a domain of its own; the daughters' keys it would hand out are dropped."""
+    import torch
+    divide_counts(plan.n_out, plan.n_keep, plan.n_src, plan.src, plan.kind, old['tl_molecules'], old['ssa_key'],
+                  new['tl_molecules'], torch.empty(ld, dtype=torch.int64, device=col.device),
+                  col.translation.seed ^ native.VK_TL_DIVIDE_DOMAIN, col.step_index, col._ssa_key_base)

@@ -189,6 +189,25 @@ class _FakeColony:
         Colony._capacity_scratch(self)
 
 
+def test_install_agents_at_the_same_capacity_moves_the_layout():
+    """Every buffer is replaced, so a graph captured before would replay into the old ones: the
+    layout word its guard compares moves although neither ``n`` nor ``ld`` did."""
+    from lens_amd.distributed import install_agents, take_agents
+    col = _FakeColony(30, (0, 30), [0.5, 1.5, 2.5], [1.0, 2.0, 3.0], [0, 1, 2], ld=5)
+    col.lattice = None
+    names = col.agent_array_names()
+    old = {name: getattr(col, name) for name in names}
+    layout = col._layout
+    idx = torch.tensor([2, 0, 1])
+    install_agents(col, names, {name: take_agents(col, name, idx) for name in names})
+    assert (col.n, col.ld) == (3, 5)
+    for name in names:
+        assert getattr(col, name) is not old[name], name
+        assert getattr(col, name).data_ptr() != old[name].data_ptr(), name
+        assert torch.equal(getattr(col, name)[..., :3], old[name][..., :3][..., idx]), name
+    assert col._layout > layout
+
+
 def _router_worker(rank, world, port, seed, q):
     from lens_amd.distributed import AgentRouter
     os.environ['MASTER_ADDR'] = '127.0.0.1'
