@@ -37,7 +37,8 @@
  *   vk_cell_step / vk_divide_*, vk_kremling_step, vk_expression_step,
  *   vk_motility_step, vk_flagella_step, vk_contact_step, vk_contact_step_channels, vk_population_plan,
  *   vk_flagella_counts, vk_divide_flagella, vk_ssa_step, vk_ssa_propensities, vk_divide_counts,
- *   vk_ssa_flagella_target, vk_colony_metrics, vk_translation_step, vk_divide_ribosomes
+ *   vk_ssa_flagella_target, vk_colony_metrics, vk_translation_step, vk_divide_ribosomes,
+ *   vk_transcription_step
  *       are introduced by the comment blocks above their declarations.
  *
  * Conventions
@@ -1080,6 +1081,146 @@ int vk_divide_ribosomes(int64_t n_out, int64_t n_src, const int32_t *src_index, 
                         const int64_t *key_src, int32_t *slots_dst, int32_t *length_dst,
                         int64_t ld_dst, int32_t max_slots, uint64_t seed, uint64_t step,
                         vk_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Stochastic transcription: RNA polymerases elongate on the chromosome's promoters
+ *
+ *   vk_transcription_step
+ *       stands where the reference runs Transcription.next_update
+ *       (vivarium/processes/transcription.py:370-553) with polymerize_step
+ *       (vivarium/library/polymerize.py:205-259), Template.binding_state / terminates_at
+ *       (polymerize.py:87-160) and Chromosome.sequences (vivarium/states/chromosome.py:248-254).
+ *       The affinity vector, elongation, the read-through rule, unocclusion and the books
+ *       (with the reference's ATP quirk) are the reference's, operation for operation.
+ *       THE ENGINE'S OWN: initiation is the direct method in vk_ssa_step's arithmetic and
+ *       Philox draws, NOT arrow's; the read-through uniform is Philox, not Python's
+ *       random.random(); the factor levels are counts / mmol_to_counts taken at the start of
+ *       the launch; the process edits the int table in place, in front of translation and the
+ *       network.  Trajectories agree with the reference in distribution only.  Restated as
+ *       per-agent Python loops by tests/transcription_ref.py.
+ *   The RNAP list is divided by vk_divide_ribosomes as it is (it copies packed words and never
+ *   looks inside them), under a seed the host mixes with VK_TX_DIVIDE_DOMAIN: THE ENGINE'S OWN
+ *   rule, the reference's `rnaps` store declares no divider.
+ * ------------------------------------------------------------------------- */
+
+#define VK_TX_MAX_SLOTS 128       /* RNAPs per agent: 128 x 64 lanes x 4 B = 32 KiB of LDS        */
+#define VK_TX_MAX_TEMPLATES 64    /* one word per (promoter, lane): 16 KiB                        */
+#define VK_TX_MAX_TERMINATORS 4
+#define VK_TX_MAX_MONOMERS 4      /* the sequence is held at 2 bits per base                      */
+#define VK_TX_MAX_SITES 4         /* binding sites per promoter                                   */
+#define VK_TX_MAX_FACTORS 4       /* thresholds per site                                          */
+#define VK_TX_MAX_AFFINITIES 1024 /* entries of the dense affinity table, all promoters: 8 KiB    */
+#define VK_TX_MAX_POSITION 0x003fffff   /* a template holds at most 2^22 - 1 bases                */
+
+/* Mixed into the seed of vk_transcription_step's draws; the host mixes VK_TX_DIVIDE_DOMAIN into
+ * the seed it hands vk_divide_ribosomes for the RNAP lists. */
+#define VK_TX_DOMAIN 0x74785f5f73746570ULL
+#define VK_TX_DIVIDE_DOMAIN 0x74785f5f64697669ULL
+
+/* One RNAP: (position << 9) | (terminator << 7) | (template << 1) | occluding. */
+#define VK_TX_PACK(position, terminator, template_index, occluding)                                    \
+    ((int32_t)(((uint32_t)(position) << 9) | ((uint32_t)(terminator) << 7) | ((uint32_t)(template_index) << 1) | \
+               ((occluding) ? 1u : 0u)))
+
+enum vk_tx_status {             /* bits OR-ed into the caller's status[] (never cleared)              */
+    VK_TX_SLOTS_FULL = 1,       /* an initiation found the list at capacity: not fired, the agent
+                                   initiates no more this step                                        */
+    VK_TX_BAD_KEY = 2,          /* the agent's key lies outside [0, 2^31): not stepped                */
+    VK_TX_NONFINITE = 4,        /* the summed propensity was inf or NaN: no more initiation this step */
+    VK_TX_OVERFLOW = 8,         /* a count would pass INT32_MAX: see below                            */
+    VK_TX_MAX_EVENTS = 16       /* the agent fired max_events initiations: no more this step          */
+};
+
+enum vk_tx_sequence { VK_TX_SEQUENCE_AUTO = 0, VK_TX_SEQUENCE_GLOBAL = 1, VK_TX_SEQUENCE_LDS = 2 };
+
+/* The model, the same for every agent.  Every pointer is a DEVICE array the caller owns; P =
+ * n_templates, promoters in promoter order.  Per-terminator arrays have VK_TX_MAX_TERMINATORS
+ * entries per promoter (entry 4 p + i is terminator i of promoter p; unused entries are 0):
+ *   copy [P]                 the promoter's copy number;
+ *   n_term [P]               1..4 terminators;
+ *   term_pos [4 P]           the terminator's position RELATIVE to the promoter,
+ *                            (terminator.position - promoter.position) * direction: strictly
+ *                            increasing, >= 1, the last one the template's length;
+ *   term_strength, term_from [4 P]   strength[i] and the reference's strength_from(i), summed on
+ *                            the host in the reference's order (polymerize.py:140-144);
+ *   prod_ptr [4 P + 1], prod_species   rows of `counts` of each terminator's products;
+ *   seq_ptr [P + 1], seq     monomer index (< n_monomers) of every base of the templates'
+ *                            RNA sequences, concatenated; seq2 the same at 2 bits per base, 16 to
+ *                            a word, base b in bits [2 (b & 15), 2 (b & 15) + 2) of word b >> 4;
+ *   site_ptr [P + 1]         the promoter's sites; thr_ptr [sites + 1] each site's thresholds in
+ *                            the reference's dict order; thr_species (row of `counts`), thr_value;
+ *   aff_ptr [P + 1], affinity [n_affinities]   one dense table per promoter, indexed in mixed
+ *                            radix by the site states: index = (..(s_0 r_1 + s_1) r_2 + ..) with
+ *                            r_j = 1 + thresholds of site j, state 0 = None, state 1 + i =
+ *                            threshold i of the site; keys the reference's dict lacks hold 0.0;
+ *   interval [n_plan], elongate [n_plan]   the sub-interval plan of the step (as translation's).
+ * sequence: VK_TX_SEQUENCE_LDS stages seq2 in LDS whenever the workgroup's 64 KiB hold it;
+ * VK_TX_SEQUENCE_GLOBAL always reads seq from global memory; VK_TX_SEQUENCE_AUTO stages only where
+ * that costs no wave of occupancy (the same number of workgroups fits a CU's 160 KiB with and
+ * without the staged words): the kernel waits on latency at few waves per CU, and a wave more
+ * hides more of it than the LDS read saves.  Same results on every path.                    */
+typedef struct {
+    int32_t n_templates, n_monomers, n_species, max_slots;
+    int32_t occlusion, rnap_species, n_plan, n_affinities;
+    int32_t atp_row, adp_row, sequence, n_bases;   /* n_bases = seq_ptr[P] */
+    const int32_t *copy, *n_term, *term_pos, *prod_ptr, *prod_species, *seq_ptr, *site_ptr, *thr_ptr,
+        *thr_species, *aff_ptr, *elongate;
+    const uint8_t *seq;
+    const uint32_t *seq2;
+    const double *term_strength, *term_from, *thr_value, *affinity, *interval;
+} vk_tx_model;
+
+/* One step for agents [0, n), one agent per lane.  Per agent: her RNAP list slots
+ * [max_slots][ld] (VK_TX_PACK words, entries [0, length[a]) in insertion order), molecules
+ * [adp_row + 1][ld] (the monomers, then ATP where it is no monomer, then ADP), her column of
+ * counts [n_species][ld] (the table vk_ssa_step steps) and mmol_to_counts[a].
+ *
+ * Once, at the start (transcription.py:385-425, polymerize.py:87-138):
+ *   level(s) = (double) counts[s] / mmol_to_counts[a] (ENGINE'S OWN: the reference reads
+ *              concentrations a deriver left);
+ *   state of a site = 1 + the first threshold i in its order with level(thr_species[i]) >=
+ *              thr_value[i], else 0 (None); affinity[p] = the promoter's table entry at her
+ *              sites' states.  Fixed over the step;
+ *   blocked[p] = the stored RNAPs of promoter p that are occluding;
+ *   free = counts[rnap_species]; limit[m] = molecules[m]; e = 0; events = 0.
+ * Per sub-interval k of the plan, in this order:
+ *   1 substrate   rnaps = free and open[p] = copy[p] - blocked[p] as they are now, before
+ *                 elongation (:429-432);
+ *   2 elongation  if elongate[k], every RNAP in list order, occluding or not (polymerize.py:
+ *                 221-252): with m = seq[seq_ptr[t] + position], if limit[m] > 0: limit[m] -= 1,
+ *                 position += 1; if the new position is term_pos of her terminator index i: at the
+ *                 last terminator she terminates; else one draw e (u1 of its block, e += 1),
+ *                 choice = u1 * term_from[i], she terminates iff choice <= term_strength[i], else
+ *                 her terminator index becomes i + 1.  A termination adds 1 to every product of
+ *                 that terminator and to free, she leaves the list and the order of the rest is
+ *                 kept.  An RNAP whose monomer is exhausted stalls in place; the earlier in the
+ *                 list takes the last monomer.  A step onto a terminator whose products or free
+ *                 stand at INT32_MAX is VK_TX_OVERFLOW: it is not made (no monomer taken, no
+ *                 draw) and the agent does nothing more this step but the books below;
+ *   3 initiation  the direct method over interval[k], as vk_translation_step's with
+ *                 a_p = (affinity[p] * (double) open[p]) * (double) rnaps, 0 when either count
+ *                 is < 1; key (seed ^ VK_TX_DOMAIN), counter (step, (int32) keys[a], e, 0); e
+ *                 counts EVERY draw of the agent's step, read-through draws included, in the order
+ *                 they are made.  A fired p: blocked[p] += 1, rnaps -= 1, free -= 1,
+ *                 VK_TX_PACK(0, 0, p, 1) is appended (it first elongates in sub-interval k + 1),
+ *                 events += 1; VK_TX_SLOTS_FULL, VK_TX_NONFINITE and VK_TX_MAX_EVENTS as
+ *                 translation's bits;
+ *   4 unocclusion every occluding RNAP with position >= occlusion becomes polymerizing and
+ *                 blocked[her own template] -= 1 (:487-494).
+ * Then (the reference's books, :504-516): counts[rnap_species] = free; with used[m] the monomers
+ * taken, molecules[m] -= used[m] for every monomer BUT ATP, molecules[atp_row] -= sum of used
+ * (the reference overwrites ATP's own entry: not used[ATP] + sum), molecules[adp_row] += sum.
+ * Within the step limit[ATP] falls by used[ATP] only, so the stored ATP may go below zero; it is
+ * kept so (a result outside int32 is clamped with VK_TX_OVERFLOW).  The list and its length are
+ * stored.  RNAPs found with t >= n_templates or position >= the template's length stall.
+ * step_counter, advance, events_out (initiations per agent), the draws' dependence on (seed,
+ * step, key, e) alone and the argument checks are vk_translation_step's.  No atomics, no host
+ * synchronisation, no wait between workgroups.                                            */
+int vk_transcription_step(const vk_tx_model *model, int64_t n_agents, int64_t ld, int32_t *slots,
+                          int32_t *length, int32_t *molecules, int32_t *counts,
+                          const double *mmol_to_counts, const int64_t *keys, uint64_t seed,
+                          int64_t *step_counter, int32_t advance, int32_t max_events,
+                          int32_t *events_out, int32_t *status, vk_stream_t stream);
 
 /* Occupancy on the device: order[k] = the agent column with the k-th smallest
  * (bin_lin[a], key[a]) (key NULL: the column index; keys distinct, < 2^32),

@@ -82,6 +82,15 @@ network's step the ribosomes elongate and bind transcripts (vk_translation_step)
 Division splits the pools with ``divide_split`` and deals the ribosomes out by a coin each
 (vk_divide_ribosomes).
 
+With a :class:`~lens_amd.transcription.TranscriptionModel` (``transcription=``, beside
+``stochastic=``; ``translation=`` is not needed) every agent carries an ordered RNAP list
+(``rnap_slots``, ``rnap_count``) and her nucleotide, ATP and ADP pools (``tx_molecules``).  In
+front of the translation launch the RNAPs elongate, read through or terminate, and bind the
+promoters whose affinity the factor levels (``ssa`` counts / ``mmol_to_counts``) switch
+(vk_transcription_step), editing the ``ssa`` counts in place: promoters -> transcripts ->
+proteins -> complexes -> motor with no host read in the step.  Division deals the RNAPs out by
+a coin each (vk_divide_ribosomes under the transcription seed) and splits the pools.
+
 With a :class:`~lens_amd.cells.CellModel` the step continues like the
 reference's deriver pass: the growth process (from the step-start state),
 then TreeMass / DeriveGlobals (``mmol_to_counts`` for the next step's
@@ -120,6 +129,8 @@ from lens_amd.rate_law_compiler import compile_rate_laws, RateLawTable
 from lens_amd.response import CellResponse, ResponseBuffers, ResponseEngine
 from lens_amd.static_field import StaticField
 from lens_amd.stochastic import StochasticEngine, StochasticModel, describe_status, flagella_target
+from lens_amd.transcription import (TranscriptionEngine, TranscriptionModel, describe_status as describe_tx_status,
+                                    unpack as unpack_rnap)
 from lens_amd.translation import (TranslationEngine, TranslationModel, describe_status as describe_tl_status,
                                   unpack as unpack_ribosome)
 
@@ -132,7 +143,7 @@ def mmol_to_counts_from_mass(mass_fg, density_g_per_L=1100.0, avogadro=N_A_LEGAC
 # Tensors sized by the capacity that are not per-agent state: Colony._capacity_scratch
 # allocates them (the first row) or drops them for their users to allocate again (the second)
 CAPACITY_SCRATCH = ('bin_lin', 'bin_ix', 'env_bins', 'outflow', '_flag_expr_update', 'ssa_events', '_ssa_status',
-                    'tl_events', '_tl_status',
+                    'tl_events', '_tl_status', 'tx_events', '_tx_status',
                     '_counts_alt', 'flux_steps', 'counts_steps', 'nsteps_steps', '_colony_shape')
 
 
@@ -145,6 +156,7 @@ class Colony:
     _flag_expression = _flag_flags = None        # FlagellaModel(expression=...) / (complexes=...)
     stochastic = _ssa = ssa = ssa_key = None     # Colony(stochastic=...)
     translation = _tl = ribosome_slots = ribosome_count = tl_molecules = None    # Colony(translation=...)
+    transcription = _tx = rnap_slots = rnap_count = tx_molecules = None    # Colony(transcription=...)
     _x_stream = _p_stream = None                 # capture(overlap=True)
     _counts_alt = flux_steps = counts_steps = nsteps_steps = None    # capture(overlap=True), step_many
     _colony_shape = None                         # colony_metrics
@@ -156,7 +168,8 @@ class Colony:
                  table: Optional[RateLawTable] = None, specialize: bool = False,
                  cells: Optional[CellModel] = None, agent_ids=None, motility: Optional[MotilityModel] = None,
                  mechanics: Optional[ContactModel] = None, response: Optional[CellResponse] = None,
-                 stochastic: Optional[StochasticModel] = None, translation: Optional[TranslationModel] = None):
+                 stochastic: Optional[StochasticModel] = None, translation: Optional[TranslationModel] = None,
+                 transcription: Optional[TranscriptionModel] = None):
         if integrator not in ('euler', 'dopri5'):
             raise ValueError('integrator must be euler or dopri5')
         if exchange not in ('sorted', 'atomic'):
@@ -217,6 +230,15 @@ class Colony:
                 raise ValueError('translation needs a colony with stochastic=StochasticModel(...): its transcripts, '
                                  'proteins and free ribosomes are species of that table')
             translation.bind(stochastic)         # ValueError: the table lacks a species
+        if transcription is not None:
+            # checked before anything is built, like translation: the transcripts, the factors and
+            # the free RNAP are species of the stochastic table (translation= is not needed)
+            if not isinstance(transcription, TranscriptionModel):
+                raise ValueError('transcription must be a TranscriptionModel')
+            if stochastic is None:
+                raise ValueError('transcription needs a colony with stochastic=StochasticModel(...): its transcripts, '
+                                 'factors and free RNA polymerases are species of that table')
+            transcription.bind(stochastic)       # ValueError: the table lacks a species
         if mechanics is not None:
             # checked before anything is built, like motility: the contact launch moves and
             # re-bins the agents on the device, on one whole plane
@@ -331,6 +353,14 @@ class Colony:
             self.ribosome_slots = z(translation.max_ribosomes, ld, dtype=torch.int32)
             self.ribosome_count = z(ld, dtype=torch.int32)
             self.tl_molecules = z(len(translation.molecule_ids), ld, dtype=torch.int32)
+        self.transcription = transcription
+        if transcription is not None:
+            # the RNAP lists (empty), their lengths and the nucleotide pools (zero until
+            # set_transcription_molecules); the draws go by ssa_key and the ssa engine's step word
+            self._tx = TranscriptionEngine(transcription, stochastic, dev)
+            self.rnap_slots = z(transcription.max_rnaps, ld, dtype=torch.int32)
+            self.rnap_count = z(ld, dtype=torch.int32)
+            self.tx_molecules = z(len(transcription.molecule_ids), ld, dtype=torch.int32)
         if response is not None:
             self.dead = z(ld, dtype=torch.int32)
             self.frozen = z(ld, dtype=torch.int32)
@@ -455,6 +485,8 @@ class Colony:
         if getattr(self, 'translation', None) is not None:
             # the initiations of the last step; the status bits are sticky like the ones above
             self.tl_events, self._tl_status = i32(), i32()
+        if getattr(self, 'transcription', None) is not None:
+            self.tx_events, self._tx_status = i32(), i32()
         # sized by ld too, allocated by their users (capture(overlap=True), step_many, colony_metrics)
         self._counts_alt = self.flux_steps = self.counts_steps = self.nsteps_steps = None
         self._colony_shape = None
@@ -591,6 +623,49 @@ class Colony:
             if np.any(v < -2 ** 31) or np.any(v > 2 ** 31 - 1):
                 raise ValueError('set_translation_molecules: the count of %r does not fit int32' % (name,))
             self.tl_molecules[ids.index(name), :self.n].copy_(torch.from_numpy(v.astype(np.int32)))
+
+    def _need_transcription(self, what):
+        if self.transcription is None:
+            raise ValueError('%s: a colony with transcription=TranscriptionModel(...)' % what)
+
+    def rnaps(self):
+        """Host copy of the RNAP lists: per agent a list of (template, terminator, position,
+        occluding) in insertion order; ``template`` indexes the model's ``promoter_order``."""
+        self._need_transcription('rnaps')
+        slots = self.rnap_slots[:, :self.n].cpu().numpy()
+        count = self.rnap_count[:self.n].cpu().numpy()
+        return [[unpack_rnap(w) for w in slots[:count[a], a]] for a in range(self.n)]
+
+    def set_rnaps(self, lists):
+        """The RNAP list of every agent [0, n): per agent a sequence of (template, terminator,
+        position, occluding).  Copied into the existing arrays, so a captured graph sees them at
+        its next replay.  A list longer than ``max_rnaps`` or an RNAP outside its template raises."""
+        self._need_transcription('set_rnaps')
+        if len(lists) != self.n:
+            raise ValueError('set_rnaps: one list per agent (%d != %d)' % (len(lists), self.n))
+        slots = np.zeros((self.transcription.max_rnaps, self.n), dtype=np.int32)
+        count = np.zeros(self.n, dtype=np.int32)
+        for a, rnaps in enumerate(lists):
+            words = self.transcription.check_rnaps(list(rnaps))
+            slots[:len(words), a], count[a] = words, len(words)
+        self.rnap_slots[:, :self.n].copy_(torch.from_numpy(slots))
+        self.rnap_count[:self.n].copy_(torch.from_numpy(count))
+
+    def set_transcription_molecules(self, **counts):
+        """Nucleotide, ATP and ADP counts by name: an int for every agent or one value per agent
+        [0, n).  Copied into the existing ``tx_molecules`` rows."""
+        self._need_transcription('set_transcription_molecules')
+        ids = self.transcription.molecule_ids
+        for name, value in counts.items():
+            if name not in ids:
+                raise ValueError('set_transcription_molecules: no molecule %r (molecules: %s)' % (name, ids))
+            v = np.asarray(value)
+            if v.ndim and v.shape[0] < self.n:
+                raise ValueError('set_transcription_molecules: one count per agent (%d < %d)' % (v.shape[0], self.n))
+            v = np.broadcast_to(v[:self.n] if v.ndim else v, (self.n,)).astype(np.int64)
+            if np.any(v < -2 ** 31) or np.any(v > 2 ** 31 - 1):
+                raise ValueError('set_transcription_molecules: the count of %r does not fit int32' % (name,))
+            self.tx_molecules[ids.index(name), :self.n].copy_(torch.from_numpy(v.astype(np.int32)))
 
     def agent_array_names(self):
         """Every per-agent array this colony has (agent = column), as attribute names in
@@ -1203,6 +1278,8 @@ class Colony:
         counts0 = self.counts
         if self._tl is not None:
             self._tl.plan(dt)                       # the sub-interval plan is uploaded before the capture
+        if self._tx is not None:
+            self._tx.plan(dt)
         graph = torch.cuda.CUDAGraph()
         t0, s0 = self.time, self.step_index
         layout, n = self._layout, self.n
@@ -1375,6 +1452,13 @@ class Colony:
                 a = int(bad[0])
                 raise FloatingPointError('agent %d: translation step status %d (%s)' % (
                     a, int(st[a]), describe_tl_status(int(st[a]))))
+        if self._tx is not None:
+            st = self._tx_status[:self.n]
+            bad = torch.nonzero(st).flatten()
+            if bad.numel():
+                a = int(bad[0])
+                raise FloatingPointError('agent %d: transcription step status %d (%s)' % (
+                    a, int(st[a]), describe_tx_status(int(st[a]))))
 
     def _finish_step(self, dt):
         if self._flag_expression is not None:
@@ -1383,6 +1467,14 @@ class Colony:
             # the mmol_to_counts the previous step left; both before vk_cell_step touches m2c
             self._flag_expression.step(dt, self.flag_expr, self.n, update=self._flag_expr_update, accumulate=True)
             self._flagella_counts()
+        if self._tx is not None:
+            # transcription in front of translation, editing the ssa counts in place: the ribosomes
+            # below see the transcripts this step finished (the sequential order is this engine's).
+            # The factor levels are counts / mmol_to_counts with the m2c the previous step left
+            # (vk_cell_step below has not touched it yet, as _flagella_counts reads it)
+            self._tx.step(dt, self.rnap_slots, self.rnap_count, self.tx_molecules, self.ssa, self.m2c, self.ssa_key,
+                          self.n, events=self.tx_events, status=self._tx_status,
+                          step_counter=self._ssa.step_counter, advance=False)
         if self._tl is not None:
             # translation first, editing the ssa counts in place: the network below then sees the
             # proteins this step completed (the sequential order is this engine's; the reference
@@ -1563,4 +1655,10 @@ class Colony:
                                             enumerate(self.translation.molecule_ids)}
             out['ribosome_count'] = self.ribosome_count[:self.n].cpu().numpy().copy()
             out['translation_events'] = self.tl_events[:self.n].cpu().numpy().copy()
+        if self.transcription is not None:
+            m = self.tx_molecules[:, :self.n].cpu().numpy()
+            out['transcription_molecules'] = {name: m[row].copy() for row, name in
+                                              enumerate(self.transcription.molecule_ids)}
+            out['rnap_count'] = self.rnap_count[:self.n].cpu().numpy().copy()
+            out['transcription_events'] = self.tx_events[:self.n].cpu().numpy().copy()
         return out

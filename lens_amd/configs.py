@@ -387,5 +387,100 @@ def flagella_translation(data, operons=None, sequences=None, seed=SEED, **model)
                             list(AMINO_ACIDS.values()), **model)
 
 
+def _transcription_model(data, templates, sequence, affinities, **model):
+    from lens_amd.transcription import TranscriptionModel
+    domains = data.get('domains')
+    if isinstance(domains, list):                # JSON has no int keys: the fixtures hold a list
+        domains = {d['id']: d for d in domains}
+    return TranscriptionModel(sequence, templates, data.get('genes', {}), affinities,
+                              data.get('transcription_factors') or sorted(
+                                  {f for t in templates.values() for s in t.get('sites', []) for f in s['thresholds']}),
+                              model.pop('elongation_rate', data.get('elongation_rate', 10.0)),
+                              model.pop('polymerase_occlusion', data.get('polymerase_occlusion', 5)),
+                              domains=domains, **model)
+
+
+def _affinity_dict(pairs):
+    """``promoter_affinities`` of a fixture ([[promoter, state, ...], affinity] pairs) as the
+    reference's dict of tuples."""
+    return pairs if isinstance(pairs, dict) else {tuple(k): v for k, v in pairs}
+
+
+# The engine's own two-promoter chromosome of toy_transcription(): the shape of the reference's
+# toy (two promoters, directions +1 and -1, one site each, two terminators each with strengths
+# 0.5 and 1.0), not its data.
+TOY_CHROMOSOME = {
+    'sequence': 'GGATCCTAGCATTGCAAGTCCGATAGGCTTAACG',
+    'genes': {'oP': ['gP'], 'oPQ': ['gP', 'gQ'], 'oR': ['gR'], 'oRS': ['gR', 'gS']},
+    'promoters': {
+        'pP': {'id': 'pP', 'position': 2, 'direction': 1, 'sites': [{'thresholds': {'tfP': 0.2}}],
+               'terminators': [{'position': 7, 'strength': 0.5, 'products': ['oP']},
+                               {'position': 13, 'strength': 1.0, 'products': ['oPQ']}]},
+        'pR': {'id': 'pR', 'position': -2, 'direction': -1, 'sites': [{'thresholds': {'tfR': 0.4}}],
+               'terminators': [{'position': -8, 'strength': 0.5, 'products': ['oR']},
+                               {'position': -14, 'strength': 1.0, 'products': ['oRS']}]}},
+    'promoter_affinities': [[['pP', None], 1.0], [['pP', 'tfP'], 10.0], [['pR', None], 1.0], [['pR', 'tfR'], 10.0]],
+    'transcription_factors': ['tfP', 'tfR'],
+}
+
+
+def toy_transcription(data=None, **model):
+    """A toy chromosome as a :class:`~lens_amd.transcription.TranscriptionModel`: two promoters,
+    directions +1 and -1, one site each, two terminators each with strengths 0.5 and 1.0, at
+    ``elongation_rate`` 10 and ``polymerase_occlusion`` 5 (the reference's docstring example,
+    vivarium/processes/transcription.py:158-173).  ``data``: a dict of the shape of
+    tests/golden/toy_chromosome.json (the reference's ``toy_chromosome_config``, thresholds as
+    magnitudes in mM); without one, the engine's own :data:`TOY_CHROMOSOME` of the same shape.
+    Further keyword arguments (``max_rnaps``, ``seed``, ...) go to the TranscriptionModel."""
+    data = copy.deepcopy(TOY_CHROMOSOME if data is None else data)
+    return _transcription_model(data, data['promoters'], data['sequence'], _affinity_dict(data['promoter_affinities']),
+                                **model)
+
+
+def flagella_transcription(data, operons=None, sequence=None, seed=SEED, **model):
+    """The transcription process of the reference's flagella agent
+    (vivarium/compartments/flagella_expression.py:100-108) as a
+    :class:`~lens_amd.transcription.TranscriptionModel`, from a dict of the shape of
+    tests/golden/flagella_transcription.json: ``promoters`` (thresholds in mM, after the
+    reference's apply_thresholds), ``genes``, ``transcription_factors``, ``promoter_affinities``
+    ([[promoter, state, ...], affinity] pairs), ``elongation_rate`` and ``polymerase_occlusion``.
+
+    ``sequence``: the genome the promoters' positions index.  The E. coli genome is not part of
+    the reference tree, so without one (and without ``data['sequence']``) a seeded uniform random
+    genome is drawn over a COMPACT SYNTHETIC LAYOUT: the kept promoters lie one after the other,
+    each on a span of her true length (|last terminator - promoter|) and in her true direction,
+    her terminators at their true relative positions -- only the spans the promoters read exist, so
+    the absolute positions differ from the fixture's.  That is the size and the shape of the
+    reference's model, not its genes.
+
+    ``operons`` keeps only the promoters that make one of those operons: the whole pipeline
+    (15 transcripts, 49 proteins, complexes) does not fit the 64 species of a StochasticModel.  An
+    operon's transcript is the species ``<operon>_RNA`` of the stochastic table, the name
+    :func:`flagella_translation` reads.  Further keyword arguments (``max_rnaps``, ``seed`` of the
+    draws, ...) go to the TranscriptionModel."""
+    promoters = {k: copy.deepcopy(p) for k, p in data['promoters'].items()
+                 if operons is None or any(o in operons for t in p['terminators'] for o in t['products'])}
+    if not promoters:
+        raise ValueError('flagella_transcription: no promoter makes any of the operons %r' % (operons,))
+    sequence = sequence if sequence is not None else data.get('sequence')
+    if sequence is None:
+        rng = np.random.default_rng(seed)
+        base = 1                                 # position 0 stays unread: a backward slice must not end at -1
+        for p in promoters.values():
+            direction = p['direction']
+            span = (p['terminators'][-1]['position'] - p['position']) * direction
+            start = base if direction == 1 else base + span
+            for t in p['terminators']:
+                t['position'] = start + (t['position'] - p['position'])
+            p['position'] = start
+            base += span + 1
+        sequence = ''.join('ACGT'[i] for i in rng.integers(0, 4, base))
+    affinities = {k: v for k, v in _affinity_dict(data['promoter_affinities']).items() if k[0] in promoters}
+    model.setdefault('seed', seed)
+    model.setdefault('transcript_species', {o: o + '_RNA' for p in promoters.values() for t in p['terminators']
+                                            for o in t['products']})
+    return _transcription_model(data, promoters, sequence, affinities, **model)
+
+
 def deepcopy_config(cfg):
     return copy.deepcopy(cfg)

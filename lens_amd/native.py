@@ -39,7 +39,7 @@ EXPORTS = (
     'vk_ssa_step', 'vk_ssa_propensities', 'vk_divide_counts', 'vk_ssa_flagella_target',
     'vk_colonies_scratch_bytes', 'vk_colony_metrics',
     'vk_gradient_fill', 'vk_static_gather', 'vk_motility_step_static', 'vk_flagella_step_static',
-    'vk_translation_step', 'vk_divide_ribosomes',
+    'vk_translation_step', 'vk_divide_ribosomes', 'vk_transcription_step',
 )
 
 VK_CELL_MASS, VK_CELL_VOLUME, VK_CELL_LENGTH, VK_CELL_SURFACE_AREA, VK_CELL_PROTEIN, VK_CELL_ANGLE = range(6)
@@ -62,6 +62,12 @@ VK_TL_DOMAIN = 0x746c5f5f73746570                  # mixed into the seed of vk_t
 VK_TL_DIVIDE_DOMAIN = 0x746c5f5f64697669           # and of vk_divide_ribosomes' coins
 VK_TL_SLOTS_FULL, VK_TL_BAD_KEY, VK_TL_NONFINITE, VK_TL_OVERFLOW, VK_TL_MAX_EVENTS = 1, 2, 4, 8, 16
 VK_TL_RELEASE_REFERENCE, VK_TL_RELEASE_TEMPLATE = 0, 1
+VK_TX_MAX_SLOTS, VK_TX_MAX_TEMPLATES, VK_TX_MAX_TERMINATORS, VK_TX_MAX_MONOMERS = 128, 64, 4, 4
+VK_TX_MAX_SITES, VK_TX_MAX_FACTORS, VK_TX_MAX_AFFINITIES, VK_TX_MAX_POSITION = 4, 4, 1024, 0x003fffff
+VK_TX_DOMAIN = 0x74785f5f73746570                  # mixed into the seed of vk_transcription_step's draws
+VK_TX_DIVIDE_DOMAIN = 0x74785f5f64697669           # and, by the host, of the RNAP lists' division coins
+VK_TX_SLOTS_FULL, VK_TX_BAD_KEY, VK_TX_NONFINITE, VK_TX_OVERFLOW, VK_TX_MAX_EVENTS = 1, 2, 4, 8, 16
+VK_TX_SEQUENCE_AUTO, VK_TX_SEQUENCE_GLOBAL, VK_TX_SEQUENCE_LDS = 0, 1, 2
 (VK_COLONY_MASS, VK_COLONY_CELL_AREA, VK_COLONY_CX, VK_COLONY_CY, VK_COLONY_SXX, VK_COLONY_SYY, VK_COLONY_SXY,
  VK_COLONY_ANGLE, VK_COLONY_MAJOR, VK_COLONY_MINOR) = range(10)
 VK_COLONY_ROWS = 10
@@ -174,6 +180,15 @@ class VkTlModel(ctypes.Structure):
                            'interval')]
 
 
+class VkTxModel(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('n_templates', 'n_monomers', 'n_species', 'max_slots', 'occlusion',
+                                              'rnap_species', 'n_plan', 'n_affinities', 'atp_row', 'adp_row',
+                                              'sequence', 'n_bases')] + [
+        (n, _vp) for n in ('copy', 'n_term', 'term_pos', 'prod_ptr', 'prod_species', 'seq_ptr', 'site_ptr', 'thr_ptr',
+                           'thr_species', 'aff_ptr', 'elongate', 'seq', 'seq2', 'term_strength', 'term_from',
+                           'thr_value', 'affinity', 'interval')]
+
+
 class VkPass(ctypes.Structure):
     """One pass of a diffusion call's plan (vk_diffuse_plan)."""
     _fields_ = [(n, ctypes.c_int32) for n in ('k', 'src', 'dst', 'f0', 'lo', 'hi', 'in_lo', 'in_hi', 'gap_lo',
@@ -254,6 +269,8 @@ _SIGS = {
                              _i32, _i32, _vp, _vp, _vp], ctypes.c_int),
     'vk_divide_ribosomes': ([_i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, ctypes.c_uint64,
                              ctypes.c_uint64, _vp], ctypes.c_int),
+    'vk_transcription_step': ([ctypes.POINTER(VkTxModel), _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64,
+                               _vp, _i32, _i32, _vp, _vp, _vp], ctypes.c_int),
     'vk_occupancy_scratch_bytes': ([_i64], ctypes.c_int64),
     'vk_occupancy_sort': ([_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp], ctypes.c_int),
     'vk_exchange_ordered': ([_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _f64, _vp], ctypes.c_int),

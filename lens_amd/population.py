@@ -21,6 +21,7 @@ import torch
 from lens_amd import native
 from lens_amd.motility import DIVISION_MODES
 from lens_amd.stochastic import divide_agent_counts
+from lens_amd.transcription import divide_agent_nucleotides, divide_agent_rnaps
 from lens_amd.translation import divide_agent_molecules, divide_agent_ribosomes
 
 _SET, _SPLIT, _ZERO = native.VK_DIVIDE_SET, native.VK_DIVIDE_SPLIT, native.VK_DIVIDE_ZERO
@@ -64,7 +65,13 @@ STOCHASTIC_ARRAYS = (('ssa', 'counts'), ('ssa_key', 'counts'))
 # coin per (mother, entry) (vk_divide_ribosomes), and the monomers, ATP and ADP, split by
 # divide_split like the counts above (vk_divide_counts under a domain of its own)
 TRANSLATION_ARRAYS = (('ribosome_slots', 'ribosomes'), ('ribosome_count', 'ribosomes'), ('tl_molecules', 'molecules'))
-_ALL_AGENT_ARRAYS = AGENT_ARRAYS + STOCHASTIC_ARRAYS + TRANSLATION_ARRAYS
+# The per-agent arrays of Colony(transcription=...): the RNAP list ([max_rnaps][ld], one packed
+# word per RNAP, in insertion order) and its length, and the nucleotides, ATP and ADP.  They go by
+# the dividers of the rows above: 'ribosomes' deals every polymerase list a colony holds (the same
+# vk_divide_ribosomes, the RNAPs under the transcription seed), 'molecules' splits every pool
+# (divide_split, each under a domain of its own)
+TRANSCRIPTION_ARRAYS = (('rnap_slots', 'ribosomes'), ('rnap_count', 'ribosomes'), ('tx_molecules', 'molecules'))
+_ALL_AGENT_ARRAYS = AGENT_ARRAYS + STOCHASTIC_ARRAYS + TRANSLATION_ARRAYS + TRANSCRIPTION_ARRAYS
 
 
 @dataclass(frozen=True)
@@ -201,9 +208,25 @@ def divide_given(col, plan, old, new, ld):
     new['ordinal'][:plan.n_out] = plan.ordinal
 
 
+def divide_polymerases(col, plan, old, new, ld):
+    """'ribosomes': the ribosome list and the RNAP list, whichever the colony holds."""
+    if 'ribosome_slots' in old:
+        divide_agent_ribosomes(col, plan, old, new, ld)
+    if 'rnap_slots' in old:
+        divide_agent_rnaps(col, plan, old, new, ld)
+
+
+def divide_pools(col, plan, old, new, ld):
+    """'molecules': translation's monomer pools and transcription's nucleotide pools."""
+    if 'tl_molecules' in old:
+        divide_agent_molecules(col, plan, old, new, ld)
+    if 'tx_molecules' in old:
+        divide_agent_nucleotides(col, plan, old, new, ld)
+
+
 DIVIDERS = {'locations': divide_locations, 'lineage': divide_lineage, 'flagella': divide_flagella,
-            'given': divide_given, 'counts': divide_agent_counts, 'ribosomes': divide_agent_ribosomes,
-            'molecules': divide_agent_molecules}
+            'given': divide_given, 'counts': divide_agent_counts, 'ribosomes': divide_polymerases,
+            'molecules': divide_pools}
 
 
 def regather(col, plan, declared=True):
