@@ -38,7 +38,7 @@
  *   vk_motility_step, vk_flagella_step, vk_contact_step, vk_contact_step_channels, vk_population_plan,
  *   vk_flagella_counts, vk_divide_flagella, vk_ssa_step, vk_ssa_propensities, vk_divide_counts,
  *   vk_ssa_flagella_target, vk_colony_metrics, vk_translation_step, vk_divide_ribosomes,
- *   vk_transcription_step
+ *   vk_transcription_step, vk_rna_degradation_step
  *       are introduced by the comment blocks above their declarations.
  *
  * Conventions
@@ -888,6 +888,12 @@ int vk_divide_flagella(int64_t n_out, int64_t n_keep, int64_t n_src, const int32
 /* Mixed into the seed of vk_ssa_step's draws and of vk_divide_counts' coins (seed ^ this). */
 #define VK_SSA_DOMAIN 0x7373615f73746570ULL
 #define VK_SSA_DIVIDE_DOMAIN 0x7373615f64697669ULL
+/* A count table may hold further rows below the network's n_species that no reaction names
+ * (passive rows: vk_ssa_step and vk_ssa_propensities read and stage rows < n_species only).  The
+ * host divides them in chunks of at most 64 rows by vk_divide_counts launches of their own, chunk
+ * c under the seed (seed ^ VK_SSA_PASSIVE_DOMAIN) + c, with the same key_base: the daughters'
+ * keys are written again with equal values. */
+#define VK_SSA_PASSIVE_DOMAIN 0x7373615f70617373ULL
 
 enum vk_ssa_status {            /* bits OR-ed into the caller's status[] by vk_ssa_step (never cleared) */
     VK_SSA_MAX_EVENTS = 1,      /* the agent fired max_events events and was stopped there         */
@@ -1221,6 +1227,80 @@ int vk_transcription_step(const vk_tx_model *model, int64_t n_agents, int64_t ld
                           const double *mmol_to_counts, const int64_t *keys, uint64_t seed,
                           int64_t *step_counter, int32_t advance, int32_t max_events,
                           int32_t *events_out, int32_t *status, vk_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * RNA degradation: Michaelis-Menten in the endoRNAse and the transcript, with a carry
+ *
+ *   vk_rna_degradation_step
+ *       stands where the reference runs RnaDegradation.next_update
+ *       (vivarium/processes/degradation.py:136-182).  The rate law, its order of evaluation, the
+ *       fractional carry from step to step and the books with their signs (ATP RISES by a base
+ *       per nucleotide degraded and ADP FALLS, :172-178: the reference subtracts a negative
+ *       count) are the reference's.  THE ENGINE'S OWN: the clamp d <= counts[t] (the reference
+ *       would let a transcript go negative); the process edits the int table in place after
+ *       translation and in front of the network; km in mM is the reference's km * mole / fL by
+ *       this host's own factor, not by pint's conversion (not verified: lens_amd/degradation.py).
+ *       Restated as per-agent Python loops by tests/degradation_ref.py.
+ * ------------------------------------------------------------------------- */
+
+#define VK_DEG_MAX_TRANSCRIPTS 64
+#define VK_DEG_MAX_ENZYMES 8      /* their levels are held in registers                           */
+#define VK_DEG_MAX_PAIRS 256      /* (enzyme, transcript) pairs with a km                         */
+#define VK_DEG_MAX_MONOMERS 4
+#define VK_DEG_MAX_LENGTH 0x003fffff   /* bases of a transcript, as VK_TX_MAX_POSITION            */
+
+enum vk_deg_status {            /* bits OR-ed into the caller's status[] (never cleared)              */
+    VK_DEG_NONFINITE = 1,       /* mmol_to_counts is not finite or not > 0, or a total was inf or NaN */
+    VK_DEG_OVERFLOW = 2         /* a pool would leave [INT32_MIN, INT32_MAX]                          */
+};                              /* in either case NOTHING of the agent is written                     */
+
+/* The model, the same for every agent.  Every pointer is a DEVICE array the caller owns:
+ *   transcript_row [n_transcripts]   the transcript's row of `counts`, transcripts in model order;
+ *   enzyme_row [n_enzymes]           the enzyme's row of `counts`;
+ *   pair_ptr [n_transcripts + 1], pair_enzyme [n_pairs], kcat [n_pairs], km [n_pairs]
+ *                                    the pairs that name transcript t, in the reference's order of
+ *                                    catalytic_rates: the enzyme (index into enzyme_row), her kcat
+ *                                    and the pair's km in mM;
+ *   composition [4 n_transcripts]    entry 4 t + i: the bases of transcript t that are monomer i
+ *                                    (entries i >= n_monomers are 0); length [n_transcripts] their sum,
+ *                                    at most VK_DEG_MAX_LENGTH.
+ * n_rows: the rows of `counts` (a row outside [0, n_rows) reads 0 and is never written).  The
+ * molecule rows are vk_tx_model's: the monomers, then ATP where it is no monomer, then ADP. */
+typedef struct {
+    int32_t n_transcripts, n_enzymes, n_pairs, n_monomers;
+    int32_t n_rows, atp_row, adp_row, reserved;
+    const int32_t *transcript_row, *enzyme_row, *pair_ptr, *pair_enzyme, *composition, *length;
+    const double *kcat, *km;
+} vk_deg_model;
+
+/* One step of `timestep` (T) for agents [0, n), one agent per lane, on counts [n_rows][ld] (the
+ * table vk_ssa_step steps), partial [n_transcripts][ld] (the carry), molecules [adp_row + 1][ld]
+ * (transcription's pools) and m = mmol_to_counts[a].  FP64, no contraction, in exactly this order:
+ *   for every transcript t in model order: level = 0.0;
+ *     for every pair j of t in order, with e = her enzyme:
+ *       E = (double) counts[e] / m,  S = (double) counts[t] / m,
+ *       level = level + ((kcat[j] * E) * S) / (S + km[j]);
+ *     total = (level * m) * T + partial[t][a];
+ *     d = (int) trunc(total) (saturated where trunc(total) leaves int32),
+ *     partial[t][a] = total - trunc(total);
+ *     d = min(d, counts[t])                  THE ENGINE'S OWN clamp: the carry keeps only the
+ *                                            fraction, the excess that could not be degraded is dropped;
+ *   every E and S is evaluated from the counts as the launch found them.  Then the books:
+ *     counts[t] -= d;  molecules[i] += d * composition[t][i] for every monomer i;
+ *     molecules[atp_row] += d * length[t];  molecules[adp_row] -= d * length[t]
+ *   (where ATP is a monomer its row takes both; ADP may go below zero).
+ * VK_DEG_NONFINITE: m is not finite, m is not > 0, or a total is not finite.  VK_DEG_OVERFLOW
+ * (only where not NONFINITE): a pool's new value, summed in int64, leaves int32.  In either case
+ * nothing of that agent is written but her status bits and degraded_out[a] = 0.
+ * degraded_out [ld]: the sum of d over the transcripts (saturated to int32).  Columns n..ld-1 of
+ * every array are not touched.  A partial is always stored; a count or a pool only where it
+ * changed.  No LDS, no atomics, no host synchronisation.
+ * VK_ERR_ARG without a launch: a model over the VK_DEG_MAX_* limits or with a null array, n < 0,
+ * ld < n, a timestep that is negative or not finite, a null array with n > 0.           */
+int vk_rna_degradation_step(const vk_deg_model *model, int64_t n_agents, int64_t ld, double timestep,
+                            int32_t *counts, double *partial, int32_t *molecules,
+                            const double *mmol_to_counts, int32_t *degraded_out, int32_t *status,
+                            vk_stream_t stream);
 
 /* Occupancy on the device: order[k] = the agent column with the k-th smallest
  * (bin_lin[a], key[a]) (key NULL: the column index; keys distinct, < 2^32),

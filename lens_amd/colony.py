@@ -91,6 +91,15 @@ promoters whose affinity the factor levels (``ssa`` counts / ``mmol_to_counts``)
 proteins -> complexes -> motor with no host read in the step.  Division deals the RNAPs out by
 a coin each (vk_divide_ribosomes under the transcription seed) and splits the pools.
 
+With a :class:`~lens_amd.degradation.DegradationModel` (``degradation=``, beside ``stochastic=``
+and ``transcription=``, whose pools it refills) every agent also carries the fraction of each
+transcript the last step left undegraded (``deg_partial``).  After the translation launch and in
+front of the network's, in the compartment's process order, endoRNAses degrade the transcripts
+by the reference's Michaelis-Menten law (vk_rna_degradation_step), editing the ``ssa`` counts
+and the ``tx_molecules`` pools in place.  Daughters start with a carry of 0.  The table may hold
+rows that no reaction names (``StochasticModel(passive=...)``), so the whole flagella chromosome
+runs in one colony (``configs.flagella_gene_expression``).
+
 With a :class:`~lens_amd.cells.CellModel` the step continues like the
 reference's deriver pass: the growth process (from the step-start state),
 then TreeMass / DeriveGlobals (``mmol_to_counts`` for the next step's
@@ -117,6 +126,7 @@ from lens_amd import native
 from lens_amd.cells import CellModel, lineage_ids
 from lens_amd.colonies import ColonyShape, ColonyShapeModel
 from lens_amd.configs import initial_conc
+from lens_amd.degradation import DegradationEngine, DegradationModel, describe_status as describe_deg_status
 from lens_amd.expression import ExpressionEngine
 from lens_amd.kinetics import KineticsEngine
 from lens_amd.lattice import Lattice, occupancy, segment_index, whole_plane, N_A_LEGACY
@@ -143,7 +153,7 @@ def mmol_to_counts_from_mass(mass_fg, density_g_per_L=1100.0, avogadro=N_A_LEGAC
 # Tensors sized by the capacity that are not per-agent state: Colony._capacity_scratch
 # allocates them (the first row) or drops them for their users to allocate again (the second)
 CAPACITY_SCRATCH = ('bin_lin', 'bin_ix', 'env_bins', 'outflow', '_flag_expr_update', 'ssa_events', '_ssa_status',
-                    'tl_events', '_tl_status', 'tx_events', '_tx_status',
+                    'tl_events', '_tl_status', 'tx_events', '_tx_status', 'deg_degraded', '_deg_status',
                     '_counts_alt', 'flux_steps', 'counts_steps', 'nsteps_steps', '_colony_shape')
 
 
@@ -157,6 +167,7 @@ class Colony:
     stochastic = _ssa = ssa = ssa_key = None     # Colony(stochastic=...)
     translation = _tl = ribosome_slots = ribosome_count = tl_molecules = None    # Colony(translation=...)
     transcription = _tx = rnap_slots = rnap_count = tx_molecules = None    # Colony(transcription=...)
+    degradation = _deg = deg_partial = None      # Colony(degradation=...)
     _x_stream = _p_stream = None                 # capture(overlap=True)
     _counts_alt = flux_steps = counts_steps = nsteps_steps = None    # capture(overlap=True), step_many
     _colony_shape = None                         # colony_metrics
@@ -169,7 +180,8 @@ class Colony:
                  cells: Optional[CellModel] = None, agent_ids=None, motility: Optional[MotilityModel] = None,
                  mechanics: Optional[ContactModel] = None, response: Optional[CellResponse] = None,
                  stochastic: Optional[StochasticModel] = None, translation: Optional[TranslationModel] = None,
-                 transcription: Optional[TranscriptionModel] = None):
+                 transcription: Optional[TranscriptionModel] = None,
+                 degradation: Optional[DegradationModel] = None):
         if integrator not in ('euler', 'dopri5'):
             raise ValueError('integrator must be euler or dopri5')
         if exchange not in ('sorted', 'atomic'):
@@ -239,6 +251,16 @@ class Colony:
                 raise ValueError('transcription needs a colony with stochastic=StochasticModel(...): its transcripts, '
                                  'factors and free RNA polymerases are species of that table')
             transcription.bind(stochastic)       # ValueError: the table lacks a species
+        if degradation is not None:
+            # checked before anything is built: the transcripts and the enzymes are rows of the
+            # stochastic table, and the nucleotides return to transcription's pools
+            if not isinstance(degradation, DegradationModel):
+                raise ValueError('degradation must be a DegradationModel')
+            if stochastic is None or transcription is None:
+                raise ValueError('degradation needs a colony with stochastic=StochasticModel(...) and '
+                                 'transcription=TranscriptionModel(...): its transcripts and enzymes are rows of that '
+                                 'table, and the nucleotide pools are transcription\'s')
+            degradation.bind(stochastic, transcription)      # ValueError: the table lacks a species
         if mechanics is not None:
             # checked before anything is built, like motility: the contact launch moves and
             # re-bins the agents on the device, on one whole plane
@@ -361,6 +383,11 @@ class Colony:
             self.rnap_slots = z(transcription.max_rnaps, ld, dtype=torch.int32)
             self.rnap_count = z(ld, dtype=torch.int32)
             self.tx_molecules = z(len(transcription.molecule_ids), ld, dtype=torch.int32)
+        self.degradation = degradation
+        if degradation is not None:
+            # the carry of every transcript: 0, as the reference's partial_transcripts start
+            self._deg = DegradationEngine(degradation, stochastic, transcription, dev)
+            self.deg_partial = z(degradation.n_transcripts, ld)
         if response is not None:
             self.dead = z(ld, dtype=torch.int32)
             self.frozen = z(ld, dtype=torch.int32)
@@ -487,6 +514,9 @@ class Colony:
             self.tl_events, self._tl_status = i32(), i32()
         if getattr(self, 'transcription', None) is not None:
             self.tx_events, self._tx_status = i32(), i32()
+        if getattr(self, 'degradation', None) is not None:
+            # the transcripts each agent lost in the last step; sticky status bits as above
+            self.deg_degraded, self._deg_status = i32(), i32()
         # sized by ld too, allocated by their users (capture(overlap=True), step_many, colony_metrics)
         self._counts_alt = self.flux_steps = self.counts_steps = self.nsteps_steps = None
         self._colony_shape = None
@@ -1459,6 +1489,13 @@ class Colony:
                 a = int(bad[0])
                 raise FloatingPointError('agent %d: transcription step status %d (%s)' % (
                     a, int(st[a]), describe_tx_status(int(st[a]))))
+        if self._deg is not None:
+            st = self._deg_status[:self.n]
+            bad = torch.nonzero(st).flatten()
+            if bad.numel():
+                a = int(bad[0])
+                raise FloatingPointError('agent %d: degradation step status %d (%s)' % (
+                    a, int(st[a]), describe_deg_status(int(st[a]))))
 
     def _finish_step(self, dt):
         if self._flag_expression is not None:
@@ -1483,6 +1520,13 @@ class Colony:
             self._tl.step(dt, self.ribosome_slots, self.ribosome_count, self.tl_molecules, self.ssa, self.ssa_key,
                           self.n, events=self.tl_events, status=self._tl_status,
                           step_counter=self._ssa.step_counter, advance=False)
+        if self._deg is not None:
+            # degradation after translation and before the network, in the compartment's process
+            # order (the sequential order is this engine's, as above): the transcripts lose what the
+            # endoRNAses degrade, the nucleotides return to transcription's pools.  The levels are
+            # counts / mmol_to_counts with the m2c the previous step left, as transcription's
+            self._deg.step(dt, self.ssa, self.deg_partial, self.tx_molecules, self.m2c, self.n,
+                           degraded=self.deg_degraded, status=self._deg_status)
         if self._ssa is not None:
             # the stochastic network over the step, every agent on her own clock and by her own
             # key; then the flagella count the NEXT step's motor reads (the reference's
@@ -1646,7 +1690,7 @@ class Colony:
             out.setdefault('global', {})['dead'] = self.dead[:self.n].cpu().numpy().copy()
         if self.stochastic is not None:
             x = self.ssa[:, :self.n].cpu().numpy()
-            out['stochastic'] = {name: x[row].copy() for row, name in enumerate(self.stochastic.species)}
+            out['stochastic'] = {name: x[row].copy() for row, name in enumerate(self.stochastic.rows)}
             out['ssa_key'] = self.ssa_key[:self.n].cpu().numpy().copy()
             out['ssa_events'] = self.ssa_events[:self.n].cpu().numpy().copy()
         if self.translation is not None:
@@ -1661,4 +1705,6 @@ class Colony:
                                               enumerate(self.transcription.molecule_ids)}
             out['rnap_count'] = self.rnap_count[:self.n].cpu().numpy().copy()
             out['transcription_events'] = self.tx_events[:self.n].cpu().numpy().copy()
+        if self.degradation is not None:
+            out['degraded_transcripts'] = self.deg_degraded[:self.n].cpu().numpy().copy()
         return out

@@ -361,8 +361,9 @@ def flagella_translation(data, operons=None, sequences=None, seed=SEED, **model)
     are not at hand, ``estimated_length`` ({product: residues}), from which seeded uniform
     random sequences over the 20 amino acids are drawn -- the size and the shape of the
     reference's model, not its proteins.  ``operons`` keeps only those operons' transcripts:
-    the whole chromosome has 15 operons and 49 products, one species more than the 64 a
-    StochasticModel holds beside the free ribosome.  Templates are the reference's
+    the whole chromosome has 15 operons and 49 products, more than the 64 active species a
+    StochasticModel holds beside the free ribosome (as passive rows they all fit:
+    :func:`flagella_gene_expression`).  Templates are the reference's
     generate_template: one terminator at the sequence's end, the product its only product.
     An operon's transcript is the species ``<operon>_RNA`` of the stochastic table.
     Further keyword arguments (``max_ribosomes``, ``release``, ``seed`` of the draws, ...)
@@ -454,7 +455,8 @@ def flagella_transcription(data, operons=None, sequence=None, seed=SEED, **model
     reference's model, not its genes.
 
     ``operons`` keeps only the promoters that make one of those operons: the whole pipeline
-    (15 transcripts, 49 proteins, complexes) does not fit the 64 species of a StochasticModel.  An
+    (15 transcripts, 49 proteins, complexes) does not fit the 64 active species of a
+    StochasticModel (with passive rows it does: :func:`flagella_gene_expression`).  An
     operon's transcript is the species ``<operon>_RNA`` of the stochastic table, the name
     :func:`flagella_translation` reads.  Further keyword arguments (``max_rnaps``, ``seed`` of the
     draws, ...) go to the TranscriptionModel."""
@@ -480,6 +482,79 @@ def flagella_transcription(data, operons=None, sequence=None, seed=SEED, **model
     model.setdefault('transcript_species', {o: o + '_RNA' for p in promoters.values() for t in p['terminators']
                                             for o in t['products']})
     return _transcription_model(data, promoters, sequence, affinities, **model)
+
+
+def _degradation_model(data, transcription, transcripts=None):
+    from lens_amd.degradation import DegradationModel
+    kms = {e: {t: km for t, km in per.items() if transcripts is None or t in transcripts}
+           for e, per in data['michaelis_constants']['transcripts'].items()}
+    return DegradationModel.from_transcription(transcription, data['catalytic_rates'], {'transcripts': kms})
+
+
+def toy_degradation(data, **model):
+    """The reference's ``TOY_CONFIG`` (vivarium/processes/degradation.py:30-50) as a
+    :class:`~lens_amd.degradation.DegradationModel`, from a dict of the shape of
+    tests/golden/toy_degradation.json.  Further keyword arguments go to the DegradationModel."""
+    from lens_amd.degradation import DegradationModel
+    return DegradationModel(data['sequences'], data['catalytic_rates'], data['michaelis_constants'], **model)
+
+
+def flagella_degradation(data, transcription):
+    """The RNA degradation process of the reference's flagella agent
+    (vivarium/compartments/flagella_expression.py:119-128) as a
+    :class:`~lens_amd.degradation.DegradationModel`, from a dict of the shape of
+    tests/golden/flagella_degradation.json (``catalytic_rates``: endoRNAse 0.02;
+    ``michaelis_constants``: 1e-23 mol / fL per operon).  The sequences are
+    ``transcription.product_sequences()``, as the reference takes them from its Chromosome; of the
+    fixture's operons only those the transcription model makes are kept.  The transcripts carry
+    the species names of the transcription model (``<operon>_RNA``)."""
+    return _degradation_model(data, transcription, set(transcription.product_sequences()))
+
+
+def flagella_gene_expression(tx_data, tl_data, cx_data, deg_data, operons=None, seed=SEED, **kw):
+    """The four expression processes of the reference's flagella agent (``GeneExpression`` as
+    flagella_expression.py:93-137 configures it: Transcription, Translation, RnaDegradation,
+    Complexation) as what a Colony takes: ``{'stochastic', 'transcription', 'translation',
+    'degradation'}`` for ``Colony(..., **flagella_gene_expression(...))``, from the four fixtures
+    tests/golden/flagella_{transcription,translation,complexation,degradation}.json.
+
+    The reactions are the 7 complexation reactions only, and ``species`` holds the monomers and
+    the complexes they name (37 rows that vk_ssa_step stages).  Every other row is ``passive``, in
+    this order: the transcripts (``<operon>_RNA``, in the transcription model's product order),
+    the translated proteins that no reaction names (in the translation model's order), the
+    transcription factors a threshold names, the degradation enzymes, ``Ribosome``,
+    ``RNA Polymerase``, and what else the initial state's proteins name.  ``initial`` is
+    ``get_flagella_initial_state`` (flagella_expression.py:318-349) as the degradation fixture
+    records it (its ``molecules`` are pools, not rows: ``Colony.set_transcription_molecules`` /
+    ``set_translation_molecules``).  ``operons`` keeps only those operons' promoters and
+    transcripts; ``None`` is the whole chromosome.  ``max_rnaps``, ``sequence`` and
+    ``sequence_path`` go to the TranscriptionModel, ``max_ribosomes``, ``sequences`` and
+    ``release`` to the TranslationModel, ``seed`` to all three, anything else to the
+    StochasticModel."""
+    from lens_amd.stochastic import StochasticModel
+    tx_kw = {k: kw.pop(k) for k in ('max_rnaps', 'sequence', 'sequence_path') if k in kw}
+    tl_kw = {k: kw.pop(k) for k in ('max_ribosomes', 'sequences', 'release') if k in kw}
+    transcription = flagella_transcription(tx_data, operons=operons, seed=seed, **tx_kw)
+    translation = flagella_translation(tl_data, operons=operons, seed=seed, **tl_kw)
+    degradation = flagella_degradation(deg_data, transcription)
+    species = list(cx_data['monomer_ids']) + list(cx_data['complex_ids'])
+    proteins = deg_data['initial_state']['proteins']
+    passive = []
+    from lens_amd.transcription import UNBOUND_RNAP_KEY
+    from lens_amd.translation import UNBOUND_RIBOSOME_KEY
+    for name in (transcription.products + degradation.transcript_names() +
+                 [s for s in translation.species() if s != UNBOUND_RIBOSOME_KEY] + transcription.factors_used() +
+                 degradation.enzyme_order + [UNBOUND_RIBOSOME_KEY, UNBOUND_RNAP_KEY] + list(proteins)):
+        if name not in species and name not in passive:
+            passive.append(name)
+    initial = {name: count for name, count in proteins.items()}
+    initial.update({transcription.transcript_species.get(o, o): count
+                    for o, count in deg_data['initial_state']['transcripts'].items()
+                    if transcription.transcript_species.get(o, o) in passive})
+    stochastic = StochasticModel(species, cx_data['stoichiometry'], cx_data['rates'], initial=initial, seed=seed,
+                                 passive=passive, **kw)
+    return {'stochastic': stochastic, 'transcription': transcription, 'translation': translation,
+            'degradation': degradation}
 
 
 def deepcopy_config(cfg):

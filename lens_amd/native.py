@@ -39,7 +39,7 @@ EXPORTS = (
     'vk_ssa_step', 'vk_ssa_propensities', 'vk_divide_counts', 'vk_ssa_flagella_target',
     'vk_colonies_scratch_bytes', 'vk_colony_metrics',
     'vk_gradient_fill', 'vk_static_gather', 'vk_motility_step_static', 'vk_flagella_step_static',
-    'vk_translation_step', 'vk_divide_ribosomes', 'vk_transcription_step',
+    'vk_translation_step', 'vk_divide_ribosomes', 'vk_transcription_step', 'vk_rna_degradation_step',
 )
 
 VK_CELL_MASS, VK_CELL_VOLUME, VK_CELL_LENGTH, VK_CELL_SURFACE_AREA, VK_CELL_PROTEIN, VK_CELL_ANGLE = range(6)
@@ -68,6 +68,10 @@ VK_TX_DOMAIN = 0x74785f5f73746570                  # mixed into the seed of vk_t
 VK_TX_DIVIDE_DOMAIN = 0x74785f5f64697669           # and, by the host, of the RNAP lists' division coins
 VK_TX_SLOTS_FULL, VK_TX_BAD_KEY, VK_TX_NONFINITE, VK_TX_OVERFLOW, VK_TX_MAX_EVENTS = 1, 2, 4, 8, 16
 VK_TX_SEQUENCE_AUTO, VK_TX_SEQUENCE_GLOBAL, VK_TX_SEQUENCE_LDS = 0, 1, 2
+VK_DEG_MAX_TRANSCRIPTS, VK_DEG_MAX_ENZYMES, VK_DEG_MAX_PAIRS, VK_DEG_MAX_MONOMERS = 64, 8, 256, 4
+VK_DEG_MAX_LENGTH = 0x003fffff
+VK_DEG_NONFINITE, VK_DEG_OVERFLOW = 1, 2
+VK_SSA_PASSIVE_DOMAIN = 0x7373615f70617373         # mixed by the host into the seed of the passive rows' division
 (VK_COLONY_MASS, VK_COLONY_CELL_AREA, VK_COLONY_CX, VK_COLONY_CY, VK_COLONY_SXX, VK_COLONY_SYY, VK_COLONY_SXY,
  VK_COLONY_ANGLE, VK_COLONY_MAJOR, VK_COLONY_MINOR) = range(10)
 VK_COLONY_ROWS = 10
@@ -189,6 +193,13 @@ class VkTxModel(ctypes.Structure):
                            'thr_value', 'affinity', 'interval')]
 
 
+class VkDegModel(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('n_transcripts', 'n_enzymes', 'n_pairs', 'n_monomers', 'n_rows',
+                                              'atp_row', 'adp_row', 'reserved')] + [
+        (n, _vp) for n in ('transcript_row', 'enzyme_row', 'pair_ptr', 'pair_enzyme', 'composition', 'length', 'kcat',
+                           'km')]
+
+
 class VkPass(ctypes.Structure):
     """One pass of a diffusion call's plan (vk_diffuse_plan)."""
     _fields_ = [(n, ctypes.c_int32) for n in ('k', 'src', 'dst', 'f0', 'lo', 'hi', 'in_lo', 'in_hi', 'gap_lo',
@@ -271,6 +282,8 @@ _SIGS = {
                              ctypes.c_uint64, _vp], ctypes.c_int),
     'vk_transcription_step': ([ctypes.POINTER(VkTxModel), _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64,
                                _vp, _i32, _i32, _vp, _vp, _vp], ctypes.c_int),
+    'vk_rna_degradation_step': ([ctypes.POINTER(VkDegModel), _i64, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+                                ctypes.c_int),
     'vk_occupancy_scratch_bytes': ([_i64], ctypes.c_int64),
     'vk_occupancy_sort': ([_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp], ctypes.c_int),
     'vk_exchange_ordered': ([_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _f64, _vp], ctypes.c_int),

@@ -71,7 +71,11 @@ TRANSLATION_ARRAYS = (('ribosome_slots', 'ribosomes'), ('ribosome_count', 'ribos
 # vk_divide_ribosomes, the RNAPs under the transcription seed), 'molecules' splits every pool
 # (divide_split, each under a domain of its own)
 TRANSCRIPTION_ARRAYS = (('rnap_slots', 'ribosomes'), ('rnap_count', 'ribosomes'), ('tx_molecules', 'molecules'))
-_ALL_AGENT_ARRAYS = AGENT_ARRAYS + STOCHASTIC_ARRAYS + TRANSLATION_ARRAYS + TRANSCRIPTION_ARRAYS
+# The per-agent array of Colony(degradation=...): the fraction of a transcript that the last step
+# left undegraded ([n_transcripts][ld] FP64).  The reference generates the daughters' processes
+# anew, so their ``partial_transcripts`` start at 0: the plain zero divider
+DEGRADATION_ARRAYS = (('deg_partial', _ZERO),)
+_ALL_AGENT_ARRAYS = AGENT_ARRAYS + STOCHASTIC_ARRAYS + TRANSLATION_ARRAYS + TRANSCRIPTION_ARRAYS + DEGRADATION_ARRAYS
 
 
 @dataclass(frozen=True)

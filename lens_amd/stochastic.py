@@ -26,6 +26,7 @@ import numpy as np
 from lens_amd import native
 
 MAX_SPECIES, MAX_REACTIONS, MAX_ORDER = native.VK_SSA_MAX_SPECIES, native.VK_SSA_MAX_REACTIONS, native.VK_SSA_MAX_ORDER
+MAX_PASSIVE = 192                      # further rows of the count table that no reaction names
 STATUS_NAMES = ((native.VK_SSA_MAX_EVENTS, 'max_events reached'), (native.VK_SSA_NONFINITE, 'propensity not finite'),
                 (native.VK_SSA_OVERFLOW, 'a count would pass 2**31 - 1'), (native.VK_SSA_BAD_KEY, 'key outside [0, 2**31)'))
 
@@ -54,16 +55,25 @@ class StochasticModel:
     a negative entry makes the species a reactant of that order.  ``rates``:
     ``{reaction: rate}`` (or a sequence in the stoichiometry's order).  ``initial``:
     ``{species: count}`` (default 0) every agent starts with.  The reactions keep the
-    stoichiometry's order; within a reaction the species are sorted by row."""
+    stoichiometry's order; within a reaction the species are sorted by row.
+
+    ``passive``: ids of further rows of the count table, after the ``species`` rows, that no
+    reaction may name (at most 192).  The network's launches stage and read the ``species`` rows
+    only; translation, transcription and degradation may write any row (:attr:`rows`), and
+    division splits them all.  ``n_species`` and the packed arrays stay the network's own."""
 
     def __init__(self, species: Sequence[str], stoichiometry: Dict[str, Dict[str, int]], rates,
-                 initial: Optional[Dict[str, int]] = None, seed: int = 0, max_events: int = 100000):
+                 initial: Optional[Dict[str, int]] = None, seed: int = 0, max_events: int = 100000,
+                 passive: Sequence[str] = ()):
         self.species = [str(s) for s in species]
-        if len(set(self.species)) != len(self.species):
+        self.passive = [str(s) for s in passive]
+        if len(set(self.species + self.passive)) != len(self.species) + len(self.passive):
             raise ValueError('stochastic: species ids must be distinct')
         S = len(self.species)
         if not 1 <= S <= MAX_SPECIES:
             raise ValueError('stochastic: 1..%d species (got %d)' % (MAX_SPECIES, S))
+        if len(self.passive) > MAX_PASSIVE:
+            raise ValueError('stochastic: at most %d passive rows (got %d)' % (MAX_PASSIVE, len(self.passive)))
         if not isinstance(stoichiometry, dict):
             raise ValueError('stochastic: stoichiometry must be {reaction: {species: int}}')
         self.reactions = list(stoichiometry.keys())
@@ -74,6 +84,9 @@ class StochasticModel:
         self.matrix = np.zeros((R, S), dtype=np.int64)
         for r, rid in enumerate(self.reactions):
             for sp, value in stoichiometry[rid].items():
+                if sp in self.passive:
+                    raise ValueError('stochastic: reaction %r names the passive row %r (a row a reaction names '
+                                     'belongs in species)' % (rid, sp))
                 if sp not in row:
                     raise ValueError('stochastic: reaction %r names the unknown species %r' % (rid, sp))
                 v = _whole(value, 'stochastic: stoichiometry of %r in %r' % (sp, rid))
@@ -93,7 +106,8 @@ class StochasticModel:
         self.rates = np.asarray(rates, dtype=np.float64).reshape(-1)
         if self.rates.shape[0] != R or not np.all(np.isfinite(self.rates)) or np.any(self.rates < 0):
             raise ValueError('stochastic: one finite rate >= 0 per reaction')
-        self.initial = np.zeros(S, dtype=np.int32)
+        row = {s: i for i, s in enumerate(self.rows)}
+        self.initial = np.zeros(self.n_rows, dtype=np.int32)
         for sp, value in (initial or {}).items():
             if sp not in row:
                 raise ValueError('stochastic: initial names the unknown species %r' % (sp,))
@@ -133,13 +147,24 @@ class StochasticModel:
     def n_reactions(self):
         return len(self.reactions)
 
+    @property
+    def rows(self):
+        """Every row of the count table: the species, then the passive rows."""
+        return self.species + self.passive
+
+    @property
+    def n_rows(self):
+        return len(self.species) + len(self.passive)
+
     def index(self, species: str) -> int:
-        if species not in self.species:
-            raise ValueError('stochastic: no species %r (species: %s)' % (species, self.species))
-        return self.species.index(species)
+        """The row of a species or of a passive row."""
+        rows = self.rows
+        if species not in rows:
+            raise ValueError('stochastic: no species %r (species: %s)' % (species, rows))
+        return rows.index(species)
 
     def initial_counts(self, n: int, ld: int) -> np.ndarray:
-        out = np.zeros((self.n_species, ld), dtype=np.int32)
+        out = np.zeros((self.n_rows, ld), dtype=np.int32)
         out[:, :n] = self.initial[:, None]
         return out
 
@@ -176,7 +201,7 @@ class StochasticEngine:
 
     def _check_counts(self, counts, n, what):
         import torch
-        S = self.model.n_species
+        S = self.model.n_rows                    # the launches stage and read rows < n_species only
         if (not torch.is_tensor(counts) or counts.dtype != torch.int32 or counts.dim() != 2 or counts.shape[0] != S or
                 not counts.is_contiguous()):
             raise ValueError('%s: counts must be a contiguous int32 [%d, ld] device tensor' % (what, S))
@@ -189,7 +214,7 @@ class StochasticEngine:
     def step(self, duration, counts, keys, n=None, events=None, status=None, step_counter=None, max_events=None,
              seed=None):
         """One vk_ssa_step launch on the current stream for agents [0, n) of ``counts``
-        [S, ld] (int32) with ``keys`` [ld] (int64, each in [0, 2**31)).  ``step_counter`` (one
+        [n_rows, ld] (int32; passive rows are not touched) with ``keys`` [ld] (int64, each in [0, 2**31)).  ``step_counter`` (one
         device int64, default the engine's own) is read and advanced.  Returns (events
         [ld] int32, status [ld] int32: VK_SSA_* bits OR-ed in)."""
         import torch
@@ -232,16 +257,28 @@ def divide_counts(n_out, n_keep, n_src, src, kind, counts_src, key_src, counts_d
         native.stream_handle()), 'vk_divide_counts')
 
 
+def passive_seed(seed, chunk):
+    """The seed of the division launch of passive rows [S + 64 chunk, S + 64 chunk + 64)."""
+    return ((int(seed) ^ native.VK_SSA_PASSIVE_DOMAIN) + int(chunk)) & (2 ** 64 - 1)
+
+
 def divide_agent_counts(col, plan, old, new, ld):
     """The colony's divider of ``ssa`` / ``ssa_key`` (population.DIVIDERS): divide_split on every
-    species, a coin per (mother, species) keyed by the mother's key; daughters get the keys from
+    row, a coin per (mother, row) keyed by the mother's key; daughters get the keys from
     the colony's base on.  Once installed: the base moves past them, and the daughters' motors
     read their own share of the flagella complex."""
     base = col._ssa_key_base
     if base + plan.n_daughters - 1 > 2 ** 31 - 1:
         raise OverflowError('a stochastic key would pass 2**31 - 1 (the kernel puts it into a 32-bit counter word)')
-    divide_counts(plan.n_out, plan.n_keep, plan.n_src, plan.src, plan.kind, old['ssa'], old['ssa_key'], new['ssa'],
-                  new['ssa_key'], col.stochastic.seed, col.step_index, base)
+    S, rows = col.stochastic.n_species, col.stochastic.n_rows
+    divide_counts(plan.n_out, plan.n_keep, plan.n_src, plan.src, plan.kind, old['ssa'][:S], old['ssa_key'],
+                  new['ssa'][:S], new['ssa_key'], col.stochastic.seed, col.step_index, base)
+    # the passive rows, in chunks of at most 64 under seeds of their own; each launch writes the
+    # daughters' keys again, with equal values (the same key_base)
+    for chunk, lo in enumerate(range(S, rows, MAX_SPECIES)):
+        hi = min(lo + MAX_SPECIES, rows)
+        divide_counts(plan.n_out, plan.n_keep, plan.n_src, plan.src, plan.kind, old['ssa'][lo:hi], old['ssa_key'],
+                      new['ssa'][lo:hi], new['ssa_key'], passive_seed(col.stochastic.seed, chunk), col.step_index, base)
 
     def installed(col):
         col._ssa_key_base = base + plan.n_daughters

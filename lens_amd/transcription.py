@@ -139,6 +139,7 @@ class TranscriptionModel:
         self.transcript_species = {str(k): str(v) for k, v in (transcript_species or {}).items()}
         self.sequences, self.term_pos_rel, self.site_factors, self.site_thresholds = [], [], [], []
         self.terminator_products = []            # per promoter, per terminator: the species names
+        self.terminator_operons = []             # and the products' own names (the reference's operons)
         n_term = np.zeros(P, dtype=np.int32)
         term_pos = np.zeros(MAX_TERMINATORS * P, dtype=np.int32)
         term_strength, term_from = np.zeros(MAX_TERMINATORS * P), np.zeros(MAX_TERMINATORS * P)
@@ -193,6 +194,7 @@ class TranscriptionModel:
                 operons.extend(str(o) for o in t.get('products', []))
                 products.append(names)
             self.terminator_products.append(products)
+            self.terminator_operons.append([[str(o) for o in t.get('products', [])] for t in terminators])
             self.sequences.append(rna)
             self.term_pos_rel.append(rel)
             sites = list(tpl.get('sites', []))
@@ -291,6 +293,18 @@ class TranscriptionModel:
                 out.extend(x for x in f if x not in out)
         return out
 
+    def product_sequences(self):
+        """Chromosome.product_sequences (chromosome.py:256-266): ``{product: RNA}``, each product of
+        a terminator mapped to her promoter's RNA from the promoter up to that terminator; a later
+        promoter (or terminator) that names the same product overwrites an earlier one.  The keys are
+        the products' own names (the operons), not ``transcript_species``."""
+        sequences = {}
+        for rna, rel, operons in zip(self.sequences, self.term_pos_rel, self.terminator_operons):
+            for position, products in zip(rel, operons):
+                for product in products:
+                    sequences[product] = rna[:position]
+        return sequences
+
     def species(self):
         """Every species the stochastic table must hold: the products, the factors that a
         threshold names and the free RNAP."""
@@ -322,7 +336,7 @@ class TranscriptionModel:
         if not isinstance(stochastic, StochasticModel):
             raise ValueError('transcription needs a StochasticModel (stochastic=) that holds its transcripts, factors '
                              'and %r' % UNBOUND_RNAP_KEY)
-        missing = [s for s in self.species() if s not in stochastic.species]
+        missing = [s for s in self.species() if s not in stochastic.rows]
         if missing:
             raise ValueError('transcription: the StochasticModel lacks the species %s' % missing)
         prod_ptr, prod = [0], []
@@ -409,7 +423,8 @@ class TranscriptionEngine:
     def table(self, dt) -> native.VkTxModel:
         m, d = self.model, native.VkTxModel()
         interval, elongate, d.n_plan = self.plan(dt)
-        d.n_templates, d.n_monomers, d.n_species = m.n_templates, m.n_monomers, self.stochastic_model.n_species
+        # n_species bounds the rows the kernel may touch: every row of the table, passive ones included
+        d.n_templates, d.n_monomers, d.n_species = m.n_templates, m.n_monomers, self.stochastic_model.n_rows
         d.max_slots, d.occlusion, d.rnap_species = m.max_rnaps, m.polymerase_occlusion, self.rnap_species
         d.n_affinities, d.atp_row, d.adp_row, d.n_bases = len(m.affinity), m.atp_row, m.adp_row, len(m.seq)
         d.sequence = SEQUENCE[m.sequence_path]
@@ -422,7 +437,7 @@ class TranscriptionEngine:
              step_counter=None, advance=True, max_events=None, seed=None):
         """One vk_transcription_step launch on the current stream for agents [0, n): ``slots``
         [max_rnaps, ld] and ``length`` [ld] (int32), ``molecules`` [len(molecule_ids), ld],
-        ``counts`` [S, ld] (the stochastic table, edited in place), ``mmol_to_counts`` [ld]
+        ``counts`` [n_rows, ld] (the stochastic table, edited in place), ``mmol_to_counts`` [ld]
         (float64), ``keys`` [ld] (int64).  ``step_counter`` (one device int64, default the engine's
         own) is read, and advanced if ``advance``.  Returns (events [ld] int32, status [ld] int32:
         VK_TX_* bits OR-ed in)."""
@@ -430,7 +445,7 @@ class TranscriptionEngine:
         m = self.model
         ld = counts.shape[-1] if torch.is_tensor(counts) and counts.dim() == 2 else -1
         for t, rows, what in ((slots, m.max_rnaps, 'slots'), (molecules, len(m.molecule_ids), 'molecules'),
-                              (counts, self.stochastic_model.n_species, 'counts')):
+                              (counts, self.stochastic_model.n_rows, 'counts')):
             if (not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 2 or t.shape != (rows, ld) or
                     not t.is_contiguous()):
                 raise ValueError('TranscriptionEngine.step: %s must be a contiguous int32 [%d, ld] device tensor' % (

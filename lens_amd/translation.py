@@ -185,7 +185,7 @@ class TranslationModel:
         if not isinstance(stochastic, StochasticModel):
             raise ValueError('translation needs a StochasticModel (stochastic=) that holds its transcripts, proteins '
                              'and %r' % UNBOUND_RIBOSOME_KEY)
-        missing = [s for s in self.species() if s not in stochastic.species]
+        missing = [s for s in self.species() if s not in stochastic.rows]
         if missing:
             raise ValueError('translation: the StochasticModel lacks the species %s' % missing)
         operon = np.asarray([stochastic.index(self.transcript_species[o]) for o, _ in self.transcript_order],
@@ -254,7 +254,8 @@ class TranslationEngine:
     def table(self, dt) -> native.VkTlModel:
         m, d = self.model, native.VkTlModel()
         interval, elongate, d.n_plan = self.plan(dt)
-        d.n_templates, d.n_monomers, d.n_species = m.n_templates, m.n_monomers, self.stochastic_model.n_species
+        # n_species bounds the rows the kernel may touch: every row of the table, passive ones included
+        d.n_templates, d.n_monomers, d.n_species = m.n_templates, m.n_monomers, self.stochastic_model.n_rows
         d.max_slots, d.occlusion, d.release = m.max_ribosomes, m.polymerase_occlusion, RELEASE[m.release]
         d.ribosome_species = self.ribosome_species
         for k, v in self._dev.items():
@@ -266,14 +267,14 @@ class TranslationEngine:
              advance=True, max_events=None, seed=None):
         """One vk_translation_step launch on the current stream for agents [0, n): ``slots``
         [max_ribosomes, ld] and ``length`` [ld] (int32), ``molecules`` [monomers + 2, ld],
-        ``counts`` [S, ld] (the stochastic table, edited in place), ``keys`` [ld] (int64).
+        ``counts`` [n_rows, ld] (the stochastic table, edited in place), ``keys`` [ld] (int64).
         ``step_counter`` (one device int64, default the engine's own) is read, and advanced
         if ``advance``.  Returns (events [ld] int32, status [ld] int32: VK_TL_* bits OR-ed in)."""
         import torch
         m = self.model
         ld = counts.shape[-1] if torch.is_tensor(counts) and counts.dim() == 2 else -1
         for t, rows, what in ((slots, m.max_ribosomes, 'slots'), (molecules, m.n_monomers + 2, 'molecules'),
-                              (counts, self.stochastic_model.n_species, 'counts')):
+                              (counts, self.stochastic_model.n_rows, 'counts')):
             if (not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 2 or t.shape != (rows, ld) or
                     not t.is_contiguous()):
                 raise ValueError('TranslationEngine.step: %s must be a contiguous int32 [%d, ld] device tensor' % (
