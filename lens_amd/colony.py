@@ -117,6 +117,7 @@ from __future__ import annotations
 
 import ctypes
 import dataclasses
+from collections import namedtuple
 from typing import Optional
 
 import numpy as np
@@ -134,15 +135,16 @@ from lens_amd.mechanics import ContactBuffers, ContactModel, contact_step
 from lens_amd.motility import (DeviceOccupancy, MotilityModel, ROW_NAMES as MOTIL_ROW_NAMES, FLAG_ROW_NAMES,
                                FLAGI_ROW_NAMES, check_flagella_counts, flagella_step, motility_step)
 # the table of per-agent arrays and everything that re-lays a colony out (lens_amd/population.py)
-from lens_amd.population import AGENT_ARRAYS, _ALL_AGENT_ARRAYS, install, plan_population, regather
+from lens_amd.population import (AGENT_ARRAYS, POLYMERASES, _ALL_AGENT_ARRAYS, install, plan_population,
+                                 regather)
 from lens_amd.rate_law_compiler import compile_rate_laws, RateLawTable
 from lens_amd.response import CellResponse, ResponseBuffers, ResponseEngine
 from lens_amd.static_field import StaticField
 from lens_amd.stochastic import StochasticEngine, StochasticModel, describe_status, flagella_target
 from lens_amd.transcription import (TranscriptionEngine, TranscriptionModel, describe_status as describe_tx_status,
-                                    unpack as unpack_rnap)
+                                    POLYMERASE as RNAP)
 from lens_amd.translation import (TranslationEngine, TranslationModel, describe_status as describe_tl_status,
-                                  unpack as unpack_ribosome)
+                                  POLYMERASE as RIBOSOME)
 
 
 def mmol_to_counts_from_mass(mass_fg, density_g_per_L=1100.0, avogadro=N_A_LEGACY):
@@ -156,6 +158,30 @@ CAPACITY_SCRATCH = ('bin_lin', 'bin_ix', 'env_bins', 'outflow', '_flag_expr_upda
                     'tl_events', '_tl_status', 'tx_events', '_tx_status', 'deg_degraded', '_deg_status',
                     '_counts_alt', 'flux_steps', 'counts_steps', 'nsteps_steps', '_colony_shape')
 
+# The stochastic stages of a step, in step order (Colony._finish_step), by attribute name: the
+# engine, the events each agent had in the last step and her sticky status word (both capacity
+# scratch), the label and the wording of a raised status, and for the two polymerases the record of
+# their lists and pools (lens_amd/polymerize.py).  A colony has a stage if and only if it has the
+# engine.  A new stage is one row here, its launch in _finish_step and its arrays in population.py.
+Stage = namedtuple('Stage', 'engine events status label describe polymerase', defaults=(None,))
+STOCHASTIC_STAGES = (
+    Stage('_tx', 'tx_events', '_tx_status', 'transcription', describe_tx_status, RNAP),
+    Stage('_tl', 'tl_events', '_tl_status', 'translation', describe_tl_status, RIBOSOME),
+    Stage('_deg', 'deg_degraded', '_deg_status', 'degradation', describe_deg_status),
+    Stage('_ssa', 'ssa_events', '_ssa_status', 'stochastic', describe_status),
+)
+# the order in which a raised status is reported: the network's first, then by age of the stage
+_REPORT_ORDER = tuple(stage for engine in ('_ssa', '_tl', '_tx', '_deg')
+                      for stage in STOCHASTIC_STAGES if stage.engine == engine)
+# the polymerases' stages in the order of their arrays (population.POLYMERASES): snapshot()'s order
+_POLYMERASE_STAGES = tuple(stage for pol in POLYMERASES for stage in STOCHASTIC_STAGES if stage.polymerase is pol)
+
+
+def stage_attributes(stage):
+    """Every Colony attribute a stage names; all of them are None on a colony without the stage."""
+    pol = stage.polymerase
+    return (stage.engine,) + (() if pol is None else (pol.model, pol.slots, pol.count, pol.molecules))
+
 
 class Colony:
     # optional state that a colony may never get (and that objects made by Colony.__new__ lack)
@@ -164,10 +190,9 @@ class Colony:
     agent_order = None       # sort_by_bin: the reference index of the agent in each column
     attempts = None          # count_attempts
     _flag_expression = _flag_flags = None        # FlagellaModel(expression=...) / (complexes=...)
-    stochastic = _ssa = ssa = ssa_key = None     # Colony(stochastic=...)
-    translation = _tl = ribosome_slots = ribosome_count = tl_molecules = None    # Colony(translation=...)
-    transcription = _tx = rnap_slots = rnap_count = tx_molecules = None    # Colony(transcription=...)
-    degradation = _deg = deg_partial = None      # Colony(degradation=...)
+    # Colony(stochastic=..., translation=..., transcription=..., degradation=...): what the table of
+    # stages does not name; the engines, lists and pools it names are declared below the class
+    stochastic = ssa = ssa_key = degradation = deg_partial = None
     _x_stream = _p_stream = None                 # capture(overlap=True)
     _counts_alt = flux_steps = counts_steps = nsteps_steps = None    # capture(overlap=True), step_many
     _colony_shape = None                         # colony_metrics
@@ -505,18 +530,12 @@ class Colony:
         if self._flag_expression is not None:
             self._flag_expr_update = torch.zeros((len(self._flag_expression.table.outputs), ld),
                                                  dtype=torch.float64, device=dev)
-        if getattr(self, 'stochastic', None) is not None:       # objects that only borrow this hook lack it
-            # the events each agent fired in the last step; the status bits are sticky and
-            # checked before the capacity changes (population.install), so nothing is lost here
-            self.ssa_events, self._ssa_status = i32(), i32()
-        if getattr(self, 'translation', None) is not None:
-            # the initiations of the last step; the status bits are sticky like the ones above
-            self.tl_events, self._tl_status = i32(), i32()
-        if getattr(self, 'transcription', None) is not None:
-            self.tx_events, self._tx_status = i32(), i32()
-        if getattr(self, 'degradation', None) is not None:
-            # the transcripts each agent lost in the last step; sticky status bits as above
-            self.deg_degraded, self._deg_status = i32(), i32()
+        for stage in STOCHASTIC_STAGES:
+            if getattr(self, stage.engine, None) is not None:   # objects that only borrow this hook lack it
+                # what each agent fired (initiated, lost) in the last step; the status bits are sticky
+                # and checked before the capacity changes (population.install), so nothing is lost here
+                setattr(self, stage.events, i32())
+                setattr(self, stage.status, i32())
         # sized by ld too, allocated by their users (capture(overlap=True), step_many, colony_metrics)
         self._counts_alt = self.flux_steps = self.counts_steps = self.nsteps_steps = None
         self._colony_shape = None
@@ -611,91 +630,75 @@ class Colony:
                 raise ValueError('set_flagella: one count per agent (%d < %d)' % (c.shape[0], self.n))
             row.copy_(torch.from_numpy(c[:self.n].astype(np.int32)))
 
-    def _need_translation(self, what):
-        if self.translation is None:
-            raise ValueError('%s: a colony with translation=TranslationModel(...)' % what)
+    # -- the polymerase lists and pools: one implementation behind the six public methods ----------
+    def _polymerase_model(self, pol, what):
+        model = getattr(self, pol.model)
+        if model is None:
+            raise ValueError('%s: a colony with %s=%sModel(...)' % (what, pol.model, pol.model.capitalize()))
+        return model
+
+    def _lists(self, pol, what):
+        self._polymerase_model(pol, what)
+        slots = getattr(self, pol.slots)[:, :self.n].cpu().numpy()
+        count = getattr(self, pol.count)[:self.n].cpu().numpy()
+        return [[pol.unpack(w) for w in slots[:count[a], a]] for a in range(self.n)]
+
+    def _set_lists(self, pol, what, lists):
+        model = self._polymerase_model(pol, what)
+        if len(lists) != self.n:
+            raise ValueError('%s: one list per agent (%d != %d)' % (what, len(lists), self.n))
+        slots = np.zeros((getattr(model, pol.max_slots), self.n), dtype=np.int32)
+        count = np.zeros(self.n, dtype=np.int32)
+        for a, entries in enumerate(lists):
+            words = getattr(model, pol.check)(list(entries))
+            slots[:len(words), a], count[a] = words, len(words)
+        getattr(self, pol.slots)[:, :self.n].copy_(torch.from_numpy(slots))
+        getattr(self, pol.count)[:self.n].copy_(torch.from_numpy(count))
+
+    def _set_molecules(self, pol, what, counts):
+        ids = self._polymerase_model(pol, what).molecule_ids
+        for name, value in counts.items():
+            if name not in ids:
+                raise ValueError('%s: no molecule %r (molecules: %s)' % (what, name, ids))
+            v = np.asarray(value)
+            if v.ndim and v.shape[0] < self.n:
+                raise ValueError('%s: one count per agent (%d < %d)' % (what, v.shape[0], self.n))
+            v = np.broadcast_to(v[:self.n] if v.ndim else v, (self.n,)).astype(np.int64)
+            if np.any(v < -2 ** 31) or np.any(v > 2 ** 31 - 1):
+                raise ValueError('%s: the count of %r does not fit int32' % (what, name))
+            getattr(self, pol.molecules)[ids.index(name), :self.n].copy_(torch.from_numpy(v.astype(np.int32)))
 
     def ribosomes(self):
         """Host copy of the ribosome lists: per agent a list of (template, position, occluding)
         in insertion order; ``template`` indexes the model's ``transcript_order``."""
-        self._need_translation('ribosomes')
-        slots = self.ribosome_slots[:, :self.n].cpu().numpy()
-        count = self.ribosome_count[:self.n].cpu().numpy()
-        return [[unpack_ribosome(w) for w in slots[:count[a], a]] for a in range(self.n)]
+        return self._lists(RIBOSOME, 'ribosomes')
 
     def set_ribosomes(self, lists):
         """The ribosome list of every agent [0, n): per agent a sequence of (template, position,
         occluding).  Copied into the existing arrays, so a captured graph sees them at its next
         replay.  A list longer than ``max_ribosomes`` or a ribosome outside its template raises."""
-        self._need_translation('set_ribosomes')
-        if len(lists) != self.n:
-            raise ValueError('set_ribosomes: one list per agent (%d != %d)' % (len(lists), self.n))
-        slots = np.zeros((self.translation.max_ribosomes, self.n), dtype=np.int32)
-        count = np.zeros(self.n, dtype=np.int32)
-        for a, ribosomes in enumerate(lists):
-            words = self.translation.check_ribosomes(list(ribosomes))
-            slots[:len(words), a], count[a] = words, len(words)
-        self.ribosome_slots[:, :self.n].copy_(torch.from_numpy(slots))
-        self.ribosome_count[:self.n].copy_(torch.from_numpy(count))
+        self._set_lists(RIBOSOME, 'set_ribosomes', lists)
 
     def set_translation_molecules(self, **counts):
         """Monomer, ATP and ADP counts by name: an int for every agent or one value per agent
         [0, n).  Copied into the existing ``tl_molecules`` rows."""
-        self._need_translation('set_translation_molecules')
-        ids = self.translation.molecule_ids
-        for name, value in counts.items():
-            if name not in ids:
-                raise ValueError('set_translation_molecules: no molecule %r (molecules: %s)' % (name, ids))
-            v = np.asarray(value)
-            if v.ndim and v.shape[0] < self.n:
-                raise ValueError('set_translation_molecules: one count per agent (%d < %d)' % (v.shape[0], self.n))
-            v = np.broadcast_to(v[:self.n] if v.ndim else v, (self.n,)).astype(np.int64)
-            if np.any(v < -2 ** 31) or np.any(v > 2 ** 31 - 1):
-                raise ValueError('set_translation_molecules: the count of %r does not fit int32' % (name,))
-            self.tl_molecules[ids.index(name), :self.n].copy_(torch.from_numpy(v.astype(np.int32)))
-
-    def _need_transcription(self, what):
-        if self.transcription is None:
-            raise ValueError('%s: a colony with transcription=TranscriptionModel(...)' % what)
+        self._set_molecules(RIBOSOME, 'set_translation_molecules', counts)
 
     def rnaps(self):
         """Host copy of the RNAP lists: per agent a list of (template, terminator, position,
         occluding) in insertion order; ``template`` indexes the model's ``promoter_order``."""
-        self._need_transcription('rnaps')
-        slots = self.rnap_slots[:, :self.n].cpu().numpy()
-        count = self.rnap_count[:self.n].cpu().numpy()
-        return [[unpack_rnap(w) for w in slots[:count[a], a]] for a in range(self.n)]
+        return self._lists(RNAP, 'rnaps')
 
     def set_rnaps(self, lists):
         """The RNAP list of every agent [0, n): per agent a sequence of (template, terminator,
         position, occluding).  Copied into the existing arrays, so a captured graph sees them at
         its next replay.  A list longer than ``max_rnaps`` or an RNAP outside its template raises."""
-        self._need_transcription('set_rnaps')
-        if len(lists) != self.n:
-            raise ValueError('set_rnaps: one list per agent (%d != %d)' % (len(lists), self.n))
-        slots = np.zeros((self.transcription.max_rnaps, self.n), dtype=np.int32)
-        count = np.zeros(self.n, dtype=np.int32)
-        for a, rnaps in enumerate(lists):
-            words = self.transcription.check_rnaps(list(rnaps))
-            slots[:len(words), a], count[a] = words, len(words)
-        self.rnap_slots[:, :self.n].copy_(torch.from_numpy(slots))
-        self.rnap_count[:self.n].copy_(torch.from_numpy(count))
+        self._set_lists(RNAP, 'set_rnaps', lists)
 
     def set_transcription_molecules(self, **counts):
         """Nucleotide, ATP and ADP counts by name: an int for every agent or one value per agent
         [0, n).  Copied into the existing ``tx_molecules`` rows."""
-        self._need_transcription('set_transcription_molecules')
-        ids = self.transcription.molecule_ids
-        for name, value in counts.items():
-            if name not in ids:
-                raise ValueError('set_transcription_molecules: no molecule %r (molecules: %s)' % (name, ids))
-            v = np.asarray(value)
-            if v.ndim and v.shape[0] < self.n:
-                raise ValueError('set_transcription_molecules: one count per agent (%d < %d)' % (v.shape[0], self.n))
-            v = np.broadcast_to(v[:self.n] if v.ndim else v, (self.n,)).astype(np.int64)
-            if np.any(v < -2 ** 31) or np.any(v > 2 ** 31 - 1):
-                raise ValueError('set_transcription_molecules: the count of %r does not fit int32' % (name,))
-            self.tx_molecules[ids.index(name), :self.n].copy_(torch.from_numpy(v.astype(np.int32)))
+        self._set_molecules(RNAP, 'set_transcription_molecules', counts)
 
     def agent_array_names(self):
         """Every per-agent array this colony has (agent = column), as attribute names in
@@ -1306,10 +1309,9 @@ class Colony:
         if overlap and (self._counts_alt is None or self._counts_alt.shape != self.counts.shape):
             self._counts_alt = torch.zeros_like(self.counts)
         counts0 = self.counts
-        if self._tl is not None:
-            self._tl.plan(dt)                       # the sub-interval plan is uploaded before the capture
-        if self._tx is not None:
-            self._tx.plan(dt)
+        for stage in STOCHASTIC_STAGES:
+            if stage.polymerase is not None and getattr(self, stage.engine) is not None:
+                getattr(self, stage.engine).plan(dt)    # the sub-interval plan is uploaded before the capture
         graph = torch.cuda.CUDAGraph()
         t0, s0 = self.time, self.step_index
         layout, n = self._layout, self.n
@@ -1469,33 +1471,15 @@ class Colony:
         host reads from the device anyway, and by check_status)."""
         if self._ssa is None:
             return
-        st = self._ssa_status[:self.n]
-        bad = torch.nonzero(st).flatten()
-        if bad.numel():
-            a = int(bad[0])
-            raise FloatingPointError('agent %d: stochastic step status %d (%s)' % (
-                a, int(st[a]), describe_status(int(st[a]))))
-        if self._tl is not None:
-            st = self._tl_status[:self.n]
+        for stage in _REPORT_ORDER:
+            if getattr(self, stage.engine) is None:
+                continue
+            st = getattr(self, stage.status)[:self.n]
             bad = torch.nonzero(st).flatten()
             if bad.numel():
                 a = int(bad[0])
-                raise FloatingPointError('agent %d: translation step status %d (%s)' % (
-                    a, int(st[a]), describe_tl_status(int(st[a]))))
-        if self._tx is not None:
-            st = self._tx_status[:self.n]
-            bad = torch.nonzero(st).flatten()
-            if bad.numel():
-                a = int(bad[0])
-                raise FloatingPointError('agent %d: transcription step status %d (%s)' % (
-                    a, int(st[a]), describe_tx_status(int(st[a]))))
-        if self._deg is not None:
-            st = self._deg_status[:self.n]
-            bad = torch.nonzero(st).flatten()
-            if bad.numel():
-                a = int(bad[0])
-                raise FloatingPointError('agent %d: degradation step status %d (%s)' % (
-                    a, int(st[a]), describe_deg_status(int(st[a]))))
+                raise FloatingPointError('agent %d: %s step status %d (%s)' % (
+                    a, stage.label, int(st[a]), stage.describe(int(st[a]))))
 
     def _finish_step(self, dt):
         if self._flag_expression is not None:
@@ -1693,18 +1677,22 @@ class Colony:
             out['stochastic'] = {name: x[row].copy() for row, name in enumerate(self.stochastic.rows)}
             out['ssa_key'] = self.ssa_key[:self.n].cpu().numpy().copy()
             out['ssa_events'] = self.ssa_events[:self.n].cpu().numpy().copy()
-        if self.translation is not None:
-            m = self.tl_molecules[:, :self.n].cpu().numpy()
-            out['translation_molecules'] = {name: m[row].copy() for row, name in
-                                            enumerate(self.translation.molecule_ids)}
-            out['ribosome_count'] = self.ribosome_count[:self.n].cpu().numpy().copy()
-            out['translation_events'] = self.tl_events[:self.n].cpu().numpy().copy()
-        if self.transcription is not None:
-            m = self.tx_molecules[:, :self.n].cpu().numpy()
-            out['transcription_molecules'] = {name: m[row].copy() for row, name in
-                                              enumerate(self.transcription.molecule_ids)}
-            out['rnap_count'] = self.rnap_count[:self.n].cpu().numpy().copy()
-            out['transcription_events'] = self.tx_events[:self.n].cpu().numpy().copy()
+        for stage in _POLYMERASE_STAGES:
+            pol = stage.polymerase
+            if getattr(self, pol.model) is None:
+                continue
+            m = getattr(self, pol.molecules)[:, :self.n].cpu().numpy()
+            out[pol.model + '_molecules'] = {name: m[row].copy() for row, name in
+                                             enumerate(getattr(self, pol.model).molecule_ids)}
+            out[pol.count] = getattr(self, pol.count)[:self.n].cpu().numpy().copy()
+            out[pol.model + '_events'] = getattr(self, stage.events)[:self.n].cpu().numpy().copy()
         if self.degradation is not None:
             out['degraded_transcripts'] = self.deg_degraded[:self.n].cpu().numpy().copy()
         return out
+
+
+# the optional state the table of stages names: None on a colony that lacks the stage, like the
+# class-level declarations above
+for _stage in STOCHASTIC_STAGES:
+    for _name in stage_attributes(_stage):
+        setattr(Colony, _name, None)

@@ -29,6 +29,7 @@
 
 #include "vk_internal.h"
 #include "vk_philox.h"
+#include "vk_polymerize.h"     // the step word's advance, shared with the polymerase steps
 
 #define SSA_LANES 64
 
@@ -135,12 +136,6 @@ __global__ __launch_bounds__(SSA_LANES) void k_ssa_step(vk_ssa_net net, int64_t 
     if (bits) status[a] |= bits;
 }
 
-// after the step on the same stream: the next launch (the next replay of a graph) draws under
-// the next step word
-__global__ void k_ssa_advance(int64_t *step_counter) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) step_counter[0] += 1;
-}
-
 __global__ __launch_bounds__(256) void k_ssa_propensities(vk_ssa_net net, int64_t n, int64_t ld,
                                                           const int32_t *__restrict__ counts,
                                                           double *__restrict__ out) {
@@ -177,8 +172,7 @@ extern "C" int vk_ssa_step(const vk_ssa_net *net, int64_t n, int64_t ld, double 
         if (rc) return rc;
     }
     // the step word advances for an empty colony too: it counts steps, not agents
-    hipLaunchKernelGGL(k_ssa_advance, dim3(1), dim3(64), 0, s, step_counter);
-    return vk::launch_check("k_ssa_advance");
+    return pz_advance(step_counter, s);
 }
 
 extern "C" int vk_ssa_propensities(const vk_ssa_net *net, int64_t n, int64_t ld, const int32_t *counts, double *out,

@@ -11,12 +11,18 @@
 //                         levels from counts / mmol_to_counts and the in-place process order are
 //                         THE ENGINE'S OWN (see the header).
 //
-// Layout, after vk_translation.hip: each wave stages slot[j][lane] (the packed RNAPs) and one word
+// The key check, the list's staging and write-back, the initiation loop and the unocclusion sweep are
+// written out here, and are what csrc/vk_polymerize.h states once for translation: the same
+// arithmetic, order and draws, pinned by tests/transcription_ref.py.  Taken from that header, each of
+// them moved this kernel's idle step (empty lists, no free RNAP) above the parent's own timing
+// spread, so only the step word's advance is shared.
+//
+// Layout: each wave stages slot[j][lane] (the packed RNAPs) and one word
 // per (promoter, lane) in LDS, a lane only ever touching her own column, so every such access is
 // conflict-free and one wave per workgroup needs no barrier but the one after staging.  The list
 // crosses HBM once per launch ([slot][ld]: a wave's loads coalesce).
 //
-// What four monomers allow that translation's 24 did not:
+// What four monomers allow that translation's 24 do not:
 //   - limit[m] lives in four VGPRs, picked by compares on the monomer index, not in LDS;
 //   - the sequence can be staged in LDS at 2 bits per base (the flagella chromosome's 36 927 bases
 //     are 9.2 KiB), so that the per-lane load at the head of every elongation's dependent chain is
@@ -37,6 +43,7 @@
 
 #include "vk_internal.h"
 #include "vk_philox.h"
+#include "vk_polymerize.h"     // the step word's advance
 
 #define TX_LANES 64
 #define TX_LDS_BYTES 65536
@@ -281,10 +288,6 @@ __global__ __launch_bounds__(TX_LANES) void k_transcription_step(
     }
 }
 
-__global__ void k_tx_advance(int64_t *step_counter) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) step_counter[0] += 1;
-}
-
 static bool tx_model_ok(const vk_tx_model *m) {
     return m && m->n_templates >= 1 && m->n_templates <= VK_TX_MAX_TEMPLATES && m->n_monomers >= 1 &&
            m->n_monomers <= VK_TX_MAX_MONOMERS && m->n_species >= 1 && m->max_slots >= 1 &&
@@ -330,9 +333,5 @@ extern "C" int vk_transcription_step(const vk_tx_model *model, int64_t n, int64_
         const int rc = vk::launch_check("k_transcription_step");
         if (rc) return rc;
     }
-    if (advance) {
-        hipLaunchKernelGGL(k_tx_advance, dim3(1), dim3(64), 0, s, step_counter);
-        return vk::launch_check("k_tx_advance");
-    }
-    return VK_OK;
+    return advance ? pz_advance(step_counter, s) : VK_OK;
 }

@@ -8,6 +8,10 @@
 //                        Python loops by tests/translation_ref.py.
 //   k_divide_ribosomes   the engine's own divider of the list: a coin per (mother, entry).
 //
+// The list's staging and write-back, initiation and the release sweep are vk_polymerize.h's, shared
+// with transcription; this file keeps elongation (batches of four, the monomers' limits in LDS), the
+// transcripts' unbound copies, the books of the monomers and the LDS layout.
+//
 // Layout.  The template a ribosome reads, the monomer it takes and the length of the list differ
 // from lane to lane, so nothing of it can sit in registers without run-time indexing.  Each wave
 // stages slot[j][lane] (the packed ribosomes), limit[monomer][lane] and unbound[template][lane]
@@ -29,8 +33,9 @@
 
 #include "vk_internal.h"
 #include "vk_philox.h"
+#include "vk_polymerize.h"
 
-#define TL_LANES 64
+#define TL_LANES PZ_LANES
 #define TL_BATCH 4
 
 __global__ __launch_bounds__(TL_LANES) void k_translation_step(vk_tl_model mdl, int64_t n, int64_t ld,
@@ -51,13 +56,10 @@ __global__ __launch_bounds__(TL_LANES) void k_translation_step(vk_tl_model mdl, 
     const int lane = threadIdx.x;
     const int64_t a = (int64_t)blockIdx.x * TL_LANES + lane;
     const bool live = a < n;
-    const int64_t key = live ? keys[a] : 0;
-    int bits = 0;
-    if (key < 0 || key > (int64_t)INT32_MAX) bits = VK_TL_BAD_KEY;
-    bool run = live && bits == 0;            // false: the agent does nothing more but the books
-    int n_r = run ? min(max(length[a], 0), cap) : 0;
-    for (int j = 0; __any(j < n_r); ++j)
-        if (j < n_r) slot[j * TL_LANES + lane] = slots[(int64_t)j * ld + a];
+    int64_t key;
+    int bits;
+    bool run;
+    int n_r = pz_stage_list(slot, lane, a, live, ld, cap, keys, slots, length, key, bits, run);
     for (int m = 0; m < M; ++m) limit[m * TL_LANES + lane] = run ? molecules[(int64_t)m * ld + a] : 0;
     for (int i = 0; i < T; ++i) {
         const int s = ldc(mdl.operon_species, i);
@@ -140,83 +142,32 @@ __global__ __launch_bounds__(TL_LANES) void k_translation_step(vk_tl_model mdl, 
             }
             n_r = w;
         }
-        // 3 initiation: the direct method over the sub-interval, each lane on her own clock
-        double t_now = 0.0;
-        bool active = initiates && ribosomes >= 1;       // no free ribosome: nothing binds, no draw
-        while (__any(active)) {
-            const double rib = ribosomes < 1 ? 0.0 : (double)ribosomes;
-            double total = 0.0;
-            for (int i = 0; i < T; ++i) {
-                const int32_t x = unbound[i * TL_LANES + lane];
-                double a_i = ldc(mdl.affinity, i);
-                a_i = a_i * (x < 1 ? 0.0 : (double)x);
-                a_i = a_i * rib;
-                total = total + a_i;
-            }
-            if (active) {
-                if (total == 0.0) {
-                    active = false;                      // nothing can bind: no draw is consumed
-                } else if (!isfinite(total)) {
-                    bits |= VK_TL_NONFINITE;
-                    active = initiates = false;
-                }
-            }
-            double u1, u2;
-            philox_uniform_pair(seed, step, (int32_t)key, 0, e, u1, u2);
-            if (active) e += 1;
-            const double tau = -log(1.0 - u1) / total;
-            if (active && t_now + tau > interval) active = false;     // the overshooting event is discarded
-            const double thr = u2 * total;
-            int q = -1;
-            double cum = 0.0;
-            for (int i = 0; i < T; ++i) {
-                const int32_t x = unbound[i * TL_LANES + lane];
-                double a_i = ldc(mdl.affinity, i);
-                a_i = a_i * (x < 1 ? 0.0 : (double)x);
-                a_i = a_i * rib;
-                cum = cum + a_i;
-                if (q < 0 && cum > thr) q = i;
-            }
-            // u2 < 1 and cum_(T-1) == total > 0, so u2 * total rounds below total and a q is found
-            if (q < 0) q = T - 1;
-            if (active) {
-                if (n_r >= cap) {
-                    bits |= VK_TL_SLOTS_FULL;
-                    active = initiates = false;
-                } else {
-                    t_now = t_now + tau;
-                    unbound[q * TL_LANES + lane] -= 1;
-                    ribosomes -= 1;
-                    slot[n_r * TL_LANES + lane] = VK_TL_PACK(0, q, 1);
-                    ++n_r;
-                    if (++events >= max_events) {
-                        bits |= VK_TL_MAX_EVENTS;
-                        active = initiates = false;
-                    }
-                    if (ribosomes < 1) active = false;
-                }
-            }
-        }
-        free_r = ribosomes + terminated;
-        // 4 release: the occluding ribosomes that have cleared the start
-        for (int j = 0; __any(run && j < n_r); ++j) {
-            if (!run || j >= n_r) continue;
-            const uint32_t v = (uint32_t)slot[j * TL_LANES + lane];
-            if ((v & 1u) && (int)(v >> 7) >= mdl.occlusion) {
-                slot[j * TL_LANES + lane] = (int32_t)(v & ~1u);
-                const int r = mdl.release == VK_TL_RELEASE_TEMPLATE ? (int)((v >> 1) & 63u) : 0;
-                if (r < T) unbound[r * TL_LANES + lane] += 1;
-            }
-        }
+        // 3 initiation (vk_polymerize.h): a transcript's propensity is affinity x unbound copies x
+        // free ribosomes, and a binding takes one unbound copy
+        const pz_state st = pz_initiate(
+            slot, lane, T, cap, interval, seed, step, key, max_events,
+            pz_state{ribosomes, n_r, events, bits, e, initiates},
+            [affinity = mdl.affinity, unbound, lane](int i) {
+                return pz_factors{ldc(affinity, i), unbound[i * TL_LANES + lane]};
+            },
+            [unbound, lane](int q) {
+                unbound[q * TL_LANES + lane] -= 1;
+                return (int32_t)VK_TL_PACK(0, q, 1);
+            });
+        n_r = st.n_r, events = st.events, bits = st.bits, e = st.e, initiates = st.initiates;
+        free_r = st.pol + terminated;
+        // 4 release: the occluding ribosomes that have cleared the start give a transcript back
+        pz_unocclude<7>(slot, lane, run, n_r, mdl.occlusion, [release = mdl.release, unbound, lane, T](int t) {
+            const int r = release == VK_TL_RELEASE_TEMPLATE ? t : 0;
+            if (r < T) unbound[r * TL_LANES + lane] += 1;
+        });
     }
     if (!live) return;
     events_out[a] = events;
     if (bits) status[a] |= bits;
     if (!stepped) return;
     // the books: the list, the free ribosomes, the monomers, ATP and ADP
-    for (int j = 0; j < n_r; ++j) slots[(int64_t)j * ld + a] = slot[j * TL_LANES + lane];
-    length[a] = n_r;
-    counts[(int64_t)mdl.ribosome_species * ld + a] = free_r;
+    pz_store_list(slot, lane, a, ld, n_r, free_r, slots, length, counts + (int64_t)mdl.ribosome_species * ld);
     int64_t used = 0;
     for (int m = 0; m < M; ++m) {
         const int32_t now = limit[m * TL_LANES + lane], was = molecules[(int64_t)m * ld + a];
@@ -232,10 +183,6 @@ __global__ __launch_bounds__(TL_LANES) void k_translation_step(vk_tl_model mdl, 
         molecules[(int64_t)M * ld + a] = (int32_t)max(atp, (int64_t)INT32_MIN);
         molecules[(int64_t)(M + 1) * ld + a] = (int32_t)min(adp, (int64_t)INT32_MAX);
     }
-}
-
-__global__ void k_tl_advance(int64_t *step_counter) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) step_counter[0] += 1;
 }
 
 static bool tl_model_ok(const vk_tl_model *m) {
@@ -268,11 +215,7 @@ extern "C" int vk_translation_step(const vk_tl_model *model, int64_t n, int64_t 
         const int rc = vk::launch_check("k_translation_step");
         if (rc) return rc;
     }
-    if (advance) {
-        hipLaunchKernelGGL(k_tl_advance, dim3(1), dim3(64), 0, s, step_counter);
-        return vk::launch_check("k_tl_advance");
-    }
-    return VK_OK;
+    return advance ? pz_advance(step_counter, s) : VK_OK;
 }
 
 __global__ __launch_bounds__(256) void k_divide_ribosomes(int64_t n_out, int64_t n_src,

@@ -20,9 +20,10 @@ import torch
 
 from lens_amd import native
 from lens_amd.motility import DIVISION_MODES
+from lens_amd.polymerize import divide_agent_list, divide_agent_pool
 from lens_amd.stochastic import divide_agent_counts
-from lens_amd.transcription import divide_agent_nucleotides, divide_agent_rnaps
-from lens_amd.translation import divide_agent_molecules, divide_agent_ribosomes
+from lens_amd.transcription import POLYMERASE as RNAP
+from lens_amd.translation import POLYMERASE as RIBOSOME
 
 _SET, _SPLIT, _ZERO = native.VK_DIVIDE_SET, native.VK_DIVIDE_SPLIT, native.VK_DIVIDE_ZERO
 
@@ -212,20 +213,24 @@ def divide_given(col, plan, old, new, ld):
     new['ordinal'][:plan.n_out] = plan.ordinal
 
 
+POLYMERASES = (RIBOSOME, RNAP)            # the order of their rows in the table above
+
+
 def divide_polymerases(col, plan, old, new, ld):
-    """'ribosomes': the ribosome list and the RNAP list, whichever the colony holds."""
-    if 'ribosome_slots' in old:
-        divide_agent_ribosomes(col, plan, old, new, ld)
-    if 'rnap_slots' in old:
-        divide_agent_rnaps(col, plan, old, new, ld)
+    """'ribosomes': every polymerase list the colony holds, each under the seed of her own model
+    (vk_divide_ribosomes; THE ENGINE'S OWN rule for the RNAPs, whose store in the reference declares
+    no divider)."""
+    for pol in POLYMERASES:
+        if pol.slots in old:
+            divide_agent_list(col, plan, old, new, ld, pol)
 
 
 def divide_pools(col, plan, old, new, ld):
-    """'molecules': translation's monomer pools and transcription's nucleotide pools."""
-    if 'tl_molecules' in old:
-        divide_agent_molecules(col, plan, old, new, ld)
-    if 'tx_molecules' in old:
-        divide_agent_nucleotides(col, plan, old, new, ld)
+    """'molecules': translation's monomer pools and transcription's nucleotide pools, each under a
+    domain of its own."""
+    for pol in POLYMERASES:
+        if pol.molecules in old:
+            divide_agent_pool(col, plan, old, new, ld, pol.molecules, pol.model, pol.domain)
 
 
 DIVIDERS = {'locations': divide_locations, 'lineage': divide_lineage, 'flagella': divide_flagella,

@@ -41,8 +41,10 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from lens_amd import native
-from lens_amd.stochastic import StochasticModel, _whole, divide_counts
-from lens_amd.translation import divide_ribosomes, sub_intervals
+from lens_amd.polymerize import Polymerase, PolymeraseEngine, PolymeraseModel, sub_intervals    # noqa: F401
+from lens_amd.polymerize import describe_status as _describe_status, status_names
+from lens_amd.stochastic import StochasticModel, _whole
+from lens_amd.translation import divide_ribosomes
 
 MAX_SLOTS, MAX_TEMPLATES, MAX_TERMINATORS = native.VK_TX_MAX_SLOTS, native.VK_TX_MAX_TEMPLATES, native.VK_TX_MAX_TERMINATORS
 MAX_SITES, MAX_FACTORS, MAX_MONOMERS = native.VK_TX_MAX_SITES, native.VK_TX_MAX_FACTORS, native.VK_TX_MAX_MONOMERS
@@ -51,13 +53,11 @@ UNBOUND_RNAP_KEY = 'RNA Polymerase'
 NUCLEOTIDES = {'A': 'ATP', 'G': 'GTP', 'U': 'UTP', 'C': 'CTP'}
 ROOT_DOMAINS = {0: {'id': 0, 'lead': 0, 'lag': 0, 'children': []}}
 SEQUENCE = {'auto': native.VK_TX_SEQUENCE_AUTO, 'global': native.VK_TX_SEQUENCE_GLOBAL, 'lds': native.VK_TX_SEQUENCE_LDS}
-STATUS_NAMES = ((native.VK_TX_SLOTS_FULL, 'RNAP list full'), (native.VK_TX_BAD_KEY, 'key outside [0, 2**31)'),
-                (native.VK_TX_NONFINITE, 'propensity not finite'),
-                (native.VK_TX_OVERFLOW, 'a count would pass 2**31 - 1'), (native.VK_TX_MAX_EVENTS, 'max_events reached'))
+STATUS_NAMES = status_names('RNAP')
 
 
 def describe_status(bits: int) -> str:
-    return ', '.join(text for bit, text in STATUS_NAMES if bits & bit) or 'ok'
+    return _describe_status(bits, 'RNAP')
 
 
 def pack(template: int, terminator: int, position: int, occluding) -> int:
@@ -91,7 +91,7 @@ def _number(x, what):
     return x
 
 
-class TranscriptionModel:
+class TranscriptionModel(PolymeraseModel):
     """A transcription process in the reference's config shapes.
 
     ``sequence``: the chromosome's DNA; ``templates``: ``{promoter id: {'id', 'position',
@@ -108,6 +108,8 @@ class TranscriptionModel:
     the templates' bases, ``'global'`` (the byte table in global memory), ``'lds'`` (2 bits per base
     staged in LDS whenever it fits) or ``'auto'`` (staged only where that costs no occupancy); the
     results are the same."""
+
+    process = 'transcription'
 
     def __init__(self, sequence, templates, genes, promoter_affinities, transcription_factors, elongation_rate,
                  polymerase_occlusion, symbol_to_monomer: Optional[Dict[str, str]] = None,
@@ -260,30 +262,12 @@ class TranscriptionModel:
         words = np.zeros((len(seq) + 15) // 16 * 16, dtype=np.uint32)
         words[:len(seq)] = self.seq
         self.seq2 = (words.reshape(-1, 16) << (2 * np.arange(16, dtype=np.uint32))).sum(axis=1).astype(np.uint32)
-        self.elongation_rate = elongation_rate
-        if not (float(elongation_rate) > 0 and np.isfinite(float(elongation_rate))):
-            raise ValueError('transcription: elongation_rate must be finite and > 0')
-        self.polymerase_occlusion = _whole(polymerase_occlusion, 'transcription: polymerase_occlusion')
-        if not -2 ** 31 <= self.polymerase_occlusion <= 2 ** 31 - 1:
-            raise ValueError('transcription: polymerase_occlusion does not fit int32')
-        self.max_rnaps = _whole(max_rnaps, 'transcription: max_rnaps')
-        if not 1 <= self.max_rnaps <= MAX_SLOTS:
-            raise ValueError('transcription: max_rnaps must lie in 1..%d' % MAX_SLOTS)
-        self.seed = int(seed)
-        self.max_events = _whole(max_events, 'transcription: max_events')
-        if not 1 <= self.max_events <= 2 ** 31 - 1:
-            raise ValueError('transcription: max_events must lie in 1..2**31 - 1')
+        self.max_rnaps = self._check_parameters(elongation_rate, polymerase_occlusion, max_rnaps, 'max_rnaps',
+                                                MAX_SLOTS, seed, max_events)
 
     @property
     def n_templates(self):
         return len(self.promoter_order)
-
-    @property
-    def n_monomers(self):
-        return len(self.monomer_ids)
-
-    def length(self, template: int) -> int:
-        return int(self.seq_ptr[template + 1] - self.seq_ptr[template])
 
     def factors_used(self):
         """The factors a threshold names, in order of first appearance."""
@@ -348,9 +332,6 @@ class TranscriptionModel:
         return (np.asarray(prod_ptr, dtype=np.int32), np.asarray(prod, dtype=np.int32), np.asarray(thr, dtype=np.int32),
                 stochastic.index(UNBOUND_RNAP_KEY))
 
-    def plan(self, dt):
-        return sub_intervals(dt, self.elongation_rate)
-
     def check_rnaps(self, rnaps):
         """Packed words of one agent's ``[(template, terminator, position, occluding), ...]``;
         ValueError if the list does not fit, an RNAP stands outside its template or has passed the
@@ -367,29 +348,18 @@ class TranscriptionModel:
             words.append(pack(t, i, p, occluding))
         return np.asarray(words, dtype=np.uint32).view(np.int32)
 
-    def initial_molecules(self, n: int, ld: int, counts=None) -> np.ndarray:
-        out = np.zeros((len(self.molecule_ids), ld), dtype=np.int32)
-        for name, value in (counts or {}).items():
-            if name not in self.molecule_ids:
-                raise ValueError('transcription: no molecule %r (molecules: %s)' % (name, self.molecule_ids))
-            out[self.molecule_ids.index(name), :n] = np.asarray(value, dtype=np.int64)
-        return out
 
-
-class TranscriptionEngine:
+class TranscriptionEngine(PolymeraseEngine):
     """A :class:`TranscriptionModel` bound to a :class:`StochasticModel`'s table, resident on one
     GPU.  The engine holds the packed tables and the sub-interval plans as torch tensors; the
     library owns none of it."""
 
     def __init__(self, model: TranscriptionModel, stochastic_model: StochasticModel, device=None):
-        import torch
         if not isinstance(model, TranscriptionModel):
             raise ValueError('TranscriptionEngine: a TranscriptionModel')
         prod_ptr, prod, thr, self.rnap_species = model.bind(stochastic_model)      # before anything is built
-        native.load()
-        self.model, self.stochastic_model = model, stochastic_model
-        self.device = native.resolve_device(device)
-        put = lambda a: torch.from_numpy(np.ascontiguousarray(a if len(a) else np.zeros(1, dtype=a.dtype))).to(self.device)
+        super().__init__(model, stochastic_model, device)
+        put = self.put
         site_ptr, thr_ptr, thr_value = [0], [0], []
         for factors, values in zip(model.site_factors, model.site_thresholds):
             for v in values:
@@ -403,22 +373,6 @@ class TranscriptionEngine:
                      'aff_ptr': put(model.aff_ptr), 'seq': put(model.seq), 'seq2': put(model.seq2.view(np.int32)),
                      'term_strength': put(model.term_strength), 'term_from': put(model.term_from),
                      'thr_value': put(np.asarray(thr_value, dtype=np.float64)), 'affinity': put(model.affinity)}
-        self._plans = {}
-        self.step_counter = torch.zeros(1, dtype=torch.int64, device=self.device)
-
-    def plan(self, dt):
-        """The sub-interval plan of a step of ``dt`` on the device: (interval float64 [K],
-        elongate int32 [K], K).  Kept per ``dt``, so a captured graph's plan stays alive."""
-        import torch
-        dt = float(dt)
-        if not (dt >= 0.0 and np.isfinite(dt)):
-            raise ValueError('TranscriptionEngine: dt must be finite and >= 0')
-        if dt not in self._plans:
-            p = self.model.plan(dt)
-            iv = np.asarray([x for x, _ in p] or [0.0], dtype=np.float64)
-            el = np.asarray([int(y) for _, y in p] or [0], dtype=np.int32)
-            self._plans[dt] = (torch.from_numpy(iv).to(self.device), torch.from_numpy(el).to(self.device), len(p))
-        return self._plans[dt]
 
     def table(self, dt) -> native.VkTxModel:
         m, d = self.model, native.VkTxModel()
@@ -443,27 +397,11 @@ class TranscriptionEngine:
         VK_TX_* bits OR-ed in)."""
         import torch
         m = self.model
-        ld = counts.shape[-1] if torch.is_tensor(counts) and counts.dim() == 2 else -1
-        for t, rows, what in ((slots, m.max_rnaps, 'slots'), (molecules, len(m.molecule_ids), 'molecules'),
-                              (counts, self.stochastic_model.n_rows, 'counts')):
-            if (not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 2 or t.shape != (rows, ld) or
-                    not t.is_contiguous()):
-                raise ValueError('TranscriptionEngine.step: %s must be a contiguous int32 [%d, ld] device tensor' % (
-                    what, rows))
-        n = ld if n is None else int(n)
-        if not 0 <= n <= ld:
-            raise ValueError('TranscriptionEngine.step: 0 <= n <= ld')
-        if not torch.is_tensor(length) or length.dtype != torch.int32 or length.dim() != 1 or length.shape[0] < n:
-            raise ValueError('TranscriptionEngine.step: length must be an int32 device tensor over the agents')
-        if not torch.is_tensor(keys) or keys.dtype != torch.int64 or keys.dim() != 1 or keys.shape[0] < n:
-            raise ValueError('TranscriptionEngine.step: keys must be an int64 device tensor over the agents')
+        ld, n, events, status = self._check_step_tensors(slots, m.max_rnaps, length, molecules, counts, keys, n,
+                                                         events, status)
         if (not torch.is_tensor(mmol_to_counts) or mmol_to_counts.dtype != torch.float64 or mmol_to_counts.dim() != 1 or
                 mmol_to_counts.shape[0] < n or not mmol_to_counts.is_contiguous()):
             raise ValueError('TranscriptionEngine.step: mmol_to_counts must be a float64 device tensor over the agents')
-        if events is None:
-            events = torch.zeros(ld, dtype=torch.int32, device=self.device)
-        if status is None:
-            status = torch.zeros(ld, dtype=torch.int32, device=self.device)
         counter = self.step_counter if step_counter is None else step_counter
         d = self.table(dt)
         native.check(native._lib.vk_transcription_step(
@@ -481,19 +419,6 @@ def divide_rnaps(n_out, n_src, src, kind, slots_src, length_src, key_src, slots_
                      (int(seed) ^ native.VK_TX_DIVIDE_DOMAIN) & (2 ** 64 - 1), step)
 
 
-def divide_agent_rnaps(col, plan, old, new, ld):
-    """The colony's divider of ``rnap_slots`` / ``rnap_count`` (population.DIVIDERS): THE ENGINE'S
-    OWN rule (the reference's ``rnaps`` store declares none), a coin per (mother, entry) keyed by
-    the mother's key (the old ``ssa_key``)."""
-    divide_rnaps(plan.n_out, plan.n_src, plan.src, plan.kind, old['rnap_slots'], old['rnap_count'], old['ssa_key'],
-                 new['rnap_slots'], new['rnap_count'], col.transcription.seed, col.step_index)
-
-
-def divide_agent_nucleotides(col, plan, old, new, ld):
-    """The colony's divider of ``tx_molecules``: divide_split like the stochastic counts
-    (``'_divider': 'split'``, transcription.py:328-333), by the mothers' keys under a domain of its
-    own; the daughters' keys it would hand out are dropped."""
-    import torch
-    divide_counts(plan.n_out, plan.n_keep, plan.n_src, plan.src, plan.kind, old['tx_molecules'], old['ssa_key'],
-                  new['tx_molecules'], torch.empty(ld, dtype=torch.int64, device=col.device),
-                  col.transcription.seed ^ native.VK_TX_DIVIDE_DOMAIN, col.step_index, col._ssa_key_base)
+POLYMERASE = Polymerase(model='transcription', slots='rnap_slots', count='rnap_count', molecules='tx_molecules',
+                        max_slots='max_rnaps', check='check_rnaps', unpack=unpack, divide=divide_rnaps,
+                        domain=native.VK_TX_DIVIDE_DOMAIN)

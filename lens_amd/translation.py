@@ -24,18 +24,18 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from lens_amd import native
-from lens_amd.stochastic import StochasticModel, _whole, divide_counts
+from lens_amd.polymerize import Polymerase, PolymeraseEngine, PolymeraseModel, sub_intervals    # noqa: F401
+from lens_amd.polymerize import describe_status as _describe_status, status_names
+from lens_amd.stochastic import StochasticModel, _whole
 
 MAX_SLOTS, MAX_TEMPLATES, MAX_MONOMERS = native.VK_TL_MAX_SLOTS, native.VK_TL_MAX_TEMPLATES, native.VK_TL_MAX_MONOMERS
 UNBOUND_RIBOSOME_KEY = 'Ribosome'
 RELEASE = {'reference': native.VK_TL_RELEASE_REFERENCE, 'template': native.VK_TL_RELEASE_TEMPLATE}
-STATUS_NAMES = ((native.VK_TL_SLOTS_FULL, 'ribosome list full'), (native.VK_TL_BAD_KEY, 'key outside [0, 2**31)'),
-                (native.VK_TL_NONFINITE, 'propensity not finite'),
-                (native.VK_TL_OVERFLOW, 'a count would pass 2**31 - 1'), (native.VK_TL_MAX_EVENTS, 'max_events reached'))
+STATUS_NAMES = status_names('ribosome')
 
 
 def describe_status(bits: int) -> str:
-    return ', '.join(text for bit, text in STATUS_NAMES if bits & bit) or 'ok'
+    return _describe_status(bits, 'ribosome')
 
 
 def pack(template: int, position: int, occluding) -> int:
@@ -49,19 +49,7 @@ def unpack(word: int):
     return (word >> 1) & 63, word >> 7, bool(word & 1)
 
 
-def sub_intervals(dt, rate):
-    """The reference's float loop (translation.py:478-499, 533), run once: a list of
-    (interval, elongates).  A trailing partial sub-interval elongates nothing."""
-    out, time = [], 0
-    while time < dt:
-        distance = 1 / rate
-        interval = min(distance, dt - time)
-        out.append((interval, interval == distance))
-        time += interval
-    return out
-
-
-class TranslationModel:
+class TranslationModel(PolymeraseModel):
     """A translation process in the reference's config shapes.
 
     ``sequences``: ``{(operon, product): 'AWDPT...'}``; ``templates``: ``{(operon, product):
@@ -74,6 +62,8 @@ class TranslationModel:
     ``{operon: species}``, the name an operon's transcript has in the stochastic table where
     it is not the operon's own (the reference keeps transcripts and proteins in two stores, so
     an operon and its first product may share a name; one table needs two)."""
+
+    process = 'translation'
 
     def __init__(self, sequences, templates, transcript_affinities, elongation_rate, polymerase_occlusion,
                  symbol_to_monomer: Dict[str, str], molecules: Sequence[str], max_ribosomes: int = MAX_SLOTS,
@@ -149,30 +139,12 @@ class TranslationModel:
                 sorted(clash),))
         self.seq_ptr, self.prod_ptr = np.asarray(seq_ptr, dtype=np.int32), np.asarray(prod_ptr, dtype=np.int32)
         self.seq = np.asarray(seq, dtype=np.uint8)
-        self.elongation_rate = elongation_rate
-        if not (float(elongation_rate) > 0 and np.isfinite(float(elongation_rate))):
-            raise ValueError('translation: elongation_rate must be finite and > 0')
-        self.polymerase_occlusion = _whole(polymerase_occlusion, 'translation: polymerase_occlusion')
-        if not -2 ** 31 <= self.polymerase_occlusion <= 2 ** 31 - 1:
-            raise ValueError('translation: polymerase_occlusion does not fit int32')
-        self.max_ribosomes = _whole(max_ribosomes, 'translation: max_ribosomes')
-        if not 1 <= self.max_ribosomes <= MAX_SLOTS:
-            raise ValueError('translation: max_ribosomes must lie in 1..%d' % MAX_SLOTS)
-        self.seed = int(seed)
-        self.max_events = _whole(max_events, 'translation: max_events')
-        if not 1 <= self.max_events <= 2 ** 31 - 1:
-            raise ValueError('translation: max_events must lie in 1..2**31 - 1')
+        self.max_ribosomes = self._check_parameters(elongation_rate, polymerase_occlusion, max_ribosomes,
+                                                    'max_ribosomes', MAX_SLOTS, seed, max_events)
 
     @property
     def n_templates(self):
         return len(self.transcript_order)
-
-    @property
-    def n_monomers(self):
-        return len(self.monomer_ids)
-
-    def length(self, template: int) -> int:
-        return int(self.seq_ptr[template + 1] - self.seq_ptr[template])
 
     def species(self):
         """Every species the stochastic table must hold: the operons' transcripts, the
@@ -193,9 +165,6 @@ class TranslationModel:
         prod = np.asarray([stochastic.index(p) for ps in self.template_products for p in ps], dtype=np.int32)
         return operon, prod, stochastic.index(UNBOUND_RIBOSOME_KEY)
 
-    def plan(self, dt):
-        return sub_intervals(dt, self.elongation_rate)
-
     def check_ribosomes(self, ribosomes):
         """Packed words of one agent's ``[(template, position, occluding), ...]``; ValueError
         if the list does not fit or a ribosome stands outside its template."""
@@ -209,47 +178,20 @@ class TranslationModel:
             words.append(pack(t, p, occluding))
         return np.asarray(words, dtype=np.uint32).view(np.int32)
 
-    def initial_molecules(self, n: int, ld: int, counts=None) -> np.ndarray:
-        out = np.zeros((len(self.molecule_ids), ld), dtype=np.int32)
-        for name, value in (counts or {}).items():
-            if name not in self.molecule_ids:
-                raise ValueError('translation: no molecule %r (molecules: %s)' % (name, self.molecule_ids))
-            out[self.molecule_ids.index(name), :n] = np.asarray(value, dtype=np.int64)
-        return out
 
-
-class TranslationEngine:
+class TranslationEngine(PolymeraseEngine):
     """A :class:`TranslationModel` bound to a :class:`StochasticModel`'s table, resident on one
     GPU.  The engine holds the packed tables and the sub-interval plans as torch tensors; the
     library owns none of it."""
 
     def __init__(self, model: TranslationModel, stochastic_model: StochasticModel, device=None):
-        import torch
         if not isinstance(model, TranslationModel):
             raise ValueError('TranslationEngine: a TranslationModel')
         operon, prod, self.ribosome_species = model.bind(stochastic_model)      # before anything is built
-        native.load()
-        self.model, self.stochastic_model = model, stochastic_model
-        self.device = native.resolve_device(device)
-        put = lambda a: torch.from_numpy(np.ascontiguousarray(a if len(a) else np.zeros(1, dtype=a.dtype))).to(self.device)
+        super().__init__(model, stochastic_model, device)
+        put = self.put
         self._dev = {'operon_species': put(operon), 'prod_species': put(prod), 'seq_ptr': put(model.seq_ptr),
                      'prod_ptr': put(model.prod_ptr), 'seq': put(model.seq), 'affinity': put(model.affinity)}
-        self._plans = {}
-        self.step_counter = torch.zeros(1, dtype=torch.int64, device=self.device)
-
-    def plan(self, dt):
-        """The sub-interval plan of a step of ``dt`` on the device: (interval float64 [K],
-        elongate int32 [K], K).  Kept per ``dt``, so a captured graph's plan stays alive."""
-        import torch
-        dt = float(dt)
-        if not (dt >= 0.0 and np.isfinite(dt)):
-            raise ValueError('TranslationEngine: dt must be finite and >= 0')
-        if dt not in self._plans:
-            p = self.model.plan(dt)
-            iv = np.asarray([x for x, _ in p] or [0.0], dtype=np.float64)
-            el = np.asarray([int(y) for _, y in p] or [0], dtype=np.int32)
-            self._plans[dt] = (torch.from_numpy(iv).to(self.device), torch.from_numpy(el).to(self.device), len(p))
-        return self._plans[dt]
 
     def table(self, dt) -> native.VkTlModel:
         m, d = self.model, native.VkTlModel()
@@ -270,26 +212,9 @@ class TranslationEngine:
         ``counts`` [n_rows, ld] (the stochastic table, edited in place), ``keys`` [ld] (int64).
         ``step_counter`` (one device int64, default the engine's own) is read, and advanced
         if ``advance``.  Returns (events [ld] int32, status [ld] int32: VK_TL_* bits OR-ed in)."""
-        import torch
         m = self.model
-        ld = counts.shape[-1] if torch.is_tensor(counts) and counts.dim() == 2 else -1
-        for t, rows, what in ((slots, m.max_ribosomes, 'slots'), (molecules, m.n_monomers + 2, 'molecules'),
-                              (counts, self.stochastic_model.n_rows, 'counts')):
-            if (not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 2 or t.shape != (rows, ld) or
-                    not t.is_contiguous()):
-                raise ValueError('TranslationEngine.step: %s must be a contiguous int32 [%d, ld] device tensor' % (
-                    what, rows))
-        n = ld if n is None else int(n)
-        if not 0 <= n <= ld:
-            raise ValueError('TranslationEngine.step: 0 <= n <= ld')
-        if not torch.is_tensor(length) or length.dtype != torch.int32 or length.dim() != 1 or length.shape[0] < n:
-            raise ValueError('TranslationEngine.step: length must be an int32 device tensor over the agents')
-        if not torch.is_tensor(keys) or keys.dtype != torch.int64 or keys.dim() != 1 or keys.shape[0] < n:
-            raise ValueError('TranslationEngine.step: keys must be an int64 device tensor over the agents')
-        if events is None:
-            events = torch.zeros(ld, dtype=torch.int32, device=self.device)
-        if status is None:
-            status = torch.zeros(ld, dtype=torch.int32, device=self.device)
+        ld, n, events, status = self._check_step_tensors(slots, m.max_ribosomes, length, molecules, counts, keys, n,
+                                                         events, status)
         counter = self.step_counter if step_counter is None else step_counter
         d = self.table(dt)
         native.check(native._lib.vk_translation_step(
@@ -309,18 +234,6 @@ def divide_ribosomes(n_out, n_src, src, kind, slots_src, length_src, key_src, sl
         'vk_divide_ribosomes')
 
 
-def divide_agent_ribosomes(col, plan, old, new, ld):
-    """The colony's divider of ``ribosome_slots`` / ``ribosome_count`` (population.DIVIDERS): the
-    list entry by entry, a coin per (mother, entry) keyed by the mother's key (the old ``ssa_key``)."""
-    divide_ribosomes(plan.n_out, plan.n_src, plan.src, plan.kind, old['ribosome_slots'], old['ribosome_count'],
-                     old['ssa_key'], new['ribosome_slots'], new['ribosome_count'], col.translation.seed,
-                     col.step_index)
-
-
-def divide_agent_molecules(col, plan, old, new, ld):
-    """The colony's divider of ``tl_molecules``: divide_split like the stochastic counts, by the
-    mothers' keys under a domain of its own; the daughters' keys it would hand out are dropped."""
-    import torch
-    divide_counts(plan.n_out, plan.n_keep, plan.n_src, plan.src, plan.kind, old['tl_molecules'], old['ssa_key'],
-                  new['tl_molecules'], torch.empty(ld, dtype=torch.int64, device=col.device),
-                  col.translation.seed ^ native.VK_TL_DIVIDE_DOMAIN, col.step_index, col._ssa_key_base)
+POLYMERASE = Polymerase(model='translation', slots='ribosome_slots', count='ribosome_count', molecules='tl_molecules',
+                        max_slots='max_ribosomes', check='check_ribosomes', unpack=unpack, divide=divide_ribosomes,
+                        domain=native.VK_TL_DIVIDE_DOMAIN)

@@ -4,6 +4,8 @@ lattice.whole_plane reads the four band attributes of whatever it is given.  The
 of lens_amd/population.py: the dispatch of the named dividers and the order regather runs
 them in, the plan's arithmetic against the restated plan, the capacity rule and the install."""
 
+import inspect
+import re
 from types import SimpleNamespace
 
 import numpy as np
@@ -13,7 +15,8 @@ torch = pytest.importorskip('torch')
 
 import mother_machine_ref as mref
 from lens_amd import native, population
-from lens_amd.colony import AGENT_ARRAYS, CAPACITY_SCRATCH, Colony
+from lens_amd import polymerize
+from lens_amd.colony import AGENT_ARRAYS, CAPACITY_SCRATCH, STOCHASTIC_STAGES, Colony, stage_attributes
 from lens_amd.lattice import whole_plane
 
 TABLE = ['params', 'conc', 'm2c', 'flux', 'counts', 'status', 'nsteps', 'h_state', 'location', 'cell', 'divide',
@@ -207,6 +210,85 @@ def test_install_reads_the_status_words_before_the_columns_move():
     with pytest.raises(FloatingPointError, match='agent 2: stochastic step status 8'):
         population.install(col, {'conc': torch.ones(3, 6)}, 3)
     assert col.conc is conc and col.n == 4 and col._layout == 0
+
+
+def test_the_stage_table_names_declared_attributes_and_capacity_scratch():
+    for stage in STOCHASTIC_STAGES:
+        for name in stage_attributes(stage):
+            assert name in vars(Colony) and vars(Colony)[name] is None, name     # declared None at class level
+        assert stage.events in CAPACITY_SCRATCH and stage.status in CAPACITY_SCRATCH
+        pol = stage.polymerase
+        if pol is not None:
+            arrays = [name for name, _ in population._ALL_AGENT_ARRAYS]
+            assert {pol.slots, pol.count, pol.molecules} <= set(arrays)
+    assert [s.polymerase for s in STOCHASTIC_STAGES if s.polymerase] == list(population.POLYMERASES)[::-1]
+
+
+def test_the_stages_stand_in_step_order():
+    assert [s.engine for s in STOCHASTIC_STAGES] == ['_tx', '_tl', '_deg', '_ssa']
+    assert [s.label for s in STOCHASTIC_STAGES] == ['transcription', 'translation', 'degradation', 'stochastic']
+    # the statements of _finish_step that launch a stage (a line that begins with the call), in order
+    launched = re.findall(r'^\s*self\.(_\w+)\.step\(', inspect.getsource(Colony._finish_step), flags=re.M)
+    assert [e for e in launched if e != '_flag_expression'] == [s.engine for s in STOCHASTIC_STAGES]
+
+
+# the wording of every stage's status bits as it stood before the table: (label, {bit: text})
+OLD_TL = {1: 'ribosome list full', 2: 'key outside [0, 2**31)', 4: 'propensity not finite',
+          8: 'a count would pass 2**31 - 1', 16: 'max_events reached'}
+OLD_TX = {**OLD_TL, 1: 'RNAP list full'}
+STAGE_BITS = {'_ssa': ('stochastic', native.VK_SSA_OVERFLOW, 'a count would pass 2**31 - 1'),
+              '_tl': ('translation', native.VK_TL_SLOTS_FULL, 'ribosome list full'),
+              '_tx': ('transcription', native.VK_TX_SLOTS_FULL, 'RNAP list full'),
+              '_deg': ('degradation', native.VK_DEG_NONFINITE, 'mmol_to_counts not finite and > 0, or a level not finite')}
+
+
+@pytest.mark.parametrize('engine', ['_ssa', '_tl', '_tx', '_deg'])
+def test_ssa_check_names_the_stage_and_the_bit(engine):
+    """A bit in one stage's status word, on an object that has every stage: the label and the
+    description are that stage's, and the first agent with a bit is named."""
+    col = _plain_colony(4, 6)
+    for stage in STOCHASTIC_STAGES:
+        setattr(col, stage.engine, object())
+        setattr(col, stage.status, torch.zeros(6, dtype=torch.int32))
+    label, bit, text = STAGE_BITS[engine]
+    stage, = [s for s in STOCHASTIC_STAGES if s.engine == engine]
+    getattr(col, stage.status)[2] = bit
+    getattr(col, stage.status)[5] = bit                  # beyond n: not an agent
+    with pytest.raises(FloatingPointError) as err:
+        col._ssa_check()
+    assert str(err.value) == 'agent 2: %s step status %d (%s)' % (label, bit, text)
+    getattr(col, stage.status)[2] = 0
+    col._ssa_check()                                     # columns >= n are not read
+
+
+def test_ssa_check_reports_the_network_first_and_needs_the_network():
+    col = _plain_colony(4, 6)
+    for stage in STOCHASTIC_STAGES:
+        setattr(col, stage.engine, object())
+        setattr(col, stage.status, torch.full((6,), 16, dtype=torch.int32))
+    order = []
+    for _ in STOCHASTIC_STAGES:
+        with pytest.raises(FloatingPointError) as err:
+            col._ssa_check()
+        label = str(err.value).split(': ')[1].split(' step status')[0]
+        order.append(label)
+        stage, = [s for s in STOCHASTIC_STAGES if s.label == label]
+        getattr(col, stage.status).zero_()
+    assert order == ['stochastic', 'translation', 'transcription', 'degradation']
+    col._tl_status[0] = 1
+    col._ssa = None
+    col._ssa_check()                                     # no network: nothing is read
+
+
+def test_describe_status_equals_the_two_old_tables():
+    from lens_amd import transcription, translation
+    for bits in range(32):
+        for old, what, module in ((OLD_TL, 'ribosome', translation), (OLD_TX, 'RNAP', transcription)):
+            want = ', '.join(text for bit, text in old.items() if bits & bit) or 'ok'
+            assert polymerize.describe_status(bits, what) == want == module.describe_status(bits)
+            assert dict(module.STATUS_NAMES) == old
+    assert (native.VK_TL_SLOTS_FULL, native.VK_TL_BAD_KEY, native.VK_TL_NONFINITE, native.VK_TL_OVERFLOW,
+            native.VK_TL_MAX_EVENTS) == (1, 2, 4, 8, 16)
 
 
 @pytest.mark.parametrize('pad', [False, True])

@@ -288,3 +288,45 @@ def test_divide_rnaps(dev, n):
         dst2, dlen2 = torch.zeros_like(dst), torch.zeros_like(dlen)
         divide_ribosomes(*args, dst2, dlen2, model.seed, 9)
         assert not torch.equal(dlen2[:n_out], dlen[:n_out])
+
+
+def ragged_wave_case():
+    """step_case(65) at ld = 70, a full wave and a wave of one lane, arranged so that the lanes of the
+    full wave leave the shared initiation loop at different rounds: two keys outside [0, 2**31), one
+    full list that stalls (no nucleotides, nobody occluding) in front of free RNAPs, and max_events = 2.  Returns
+    (model, sm, the inputs, the restatement's two steps, its smallest margins)."""
+    n, ld = 65, 70
+    model, sm, lists, molecules, counts, m2c, keys = xref.step_case(n, cap=CAP)
+    molecules, counts = molecules[:, :ld].copy(), counts[:, :ld].copy()
+    m2c, keys = m2c[:ld].copy(), keys[:ld].copy()
+    keys[3], keys[40] = -1, 2 ** 31
+    assert len(lists[7]) == CAP
+    lists[7] = [[t, i, p, False] for t, i, p, _ in lists[7]]             # both promoters stay open
+    molecules[:4, 7] = 0
+    counts[xref.SPECIES.index('RNA Polymerase'), 7] = 4
+    l, mol, x = copy.deepcopy(lists), molecules.copy(), counts.copy()
+    status, want, worst = np.zeros(n, dtype=np.int32), [], np.full(4, np.inf)
+    for k in range(2):
+        events, status, margins = xref.step(model, model.bind(sm), l, mol, x, m2c, keys, DT, model.seed, k, status,
+                                            max_events=2)
+        worst = np.minimum(worst, margins.min(axis=0))
+        want.append((copy.deepcopy(l), mol.copy(), x.copy(), events.copy(), status.copy()))
+    return model, sm, (lists, molecules, counts, m2c, keys), want, worst
+
+
+def test_lanes_leave_the_shared_loop_at_different_rounds(dev):
+    """The status tests above run one agent at a time; here the exits of the kernel's initiation loop
+    are taken per lane under the wave-wide __any, beside neighbours that go on.  Two steps, every array bitwise against the
+    restatement, columns >= n included."""
+    from lens_amd import native
+    model, sm, (lists, molecules, counts, m2c, keys), want, worst = ragged_wave_case()
+    n = len(lists)
+    assert np.all(worst >= xref.MARGIN)                                  # no agent is left out
+    first, last = want[0], want[-1]
+    assert [a for a in range(n) if last[4][a] & native.VK_TX_BAD_KEY] == [3, 40]
+    assert first[4][7] & native.VK_TX_SLOTS_FULL and len(first[0][7]) == CAP
+    stopped = (first[4] & native.VK_TX_MAX_EVENTS) != 0
+    assert np.all(first[3][stopped] == 2) and 0 < stopped[:64].sum() < 64 and first[3][:64].min() == 0
+    assert len({int(e) for e in first[3][:64]}) == 3                    # lanes that fired 0, 1 and 2 times
+    got = _run(dev, model, sm, lists, molecules, counts, m2c, keys, n, DT, 2, max_events=2)
+    _compare(got, want, n)

@@ -256,3 +256,43 @@ def test_divide_ribosomes(dev, n):
         assert sorted(map(tuple, d0 + d1)) == sorted(map(tuple, lists[a]))
     if n >= 65:
         assert any(want[len(keep) + 2 * i] and want[len(keep) + 2 * i + 1] for i in range(len(mothers)))
+
+
+def ragged_wave_case():
+    """step_case(65) at ld = 70, a full wave and a wave of one lane, arranged so that the lanes of the
+    full wave leave the shared initiation loop at different rounds: two keys outside [0, 2**31), one
+    full list that stalls (no monomers) in front of free ribosomes, and max_events = 2.  Returns
+    (model, sm, the inputs, the restatement's two steps, its smallest margins)."""
+    n, ld = 65, 70
+    model, sm, lists, molecules, counts, keys = tref.step_case(n, cap=CAP)
+    molecules, counts, keys = molecules[:, :ld].copy(), counts[:, :ld].copy(), keys[:ld].copy()
+    keys[3], keys[40] = -1, 2 ** 31
+    assert len(lists[7]) == CAP
+    molecules[:4, 7] = 0
+    counts[[tref.SPECIES.index(s) for s in ('o1', 'o2', 'Ribosome')], 7] = 5
+    l, mol, x = copy.deepcopy(lists), molecules.copy(), counts.copy()
+    status, want, worst = np.zeros(n, dtype=np.int32), [], np.inf
+    for k in range(2):
+        events, status, margin_t, margin_q = tref.step(model, model.bind(sm), l, mol, x, keys, 1.0, model.seed, k,
+                                                       status, max_events=2)
+        worst = min(worst, margin_t.min(), margin_q.min())
+        want.append((copy.deepcopy(l), mol.copy(), x.copy(), events.copy(), status.copy()))
+    return model, sm, (lists, molecules, counts, keys), want, worst
+
+
+def test_lanes_leave_the_shared_loop_at_different_rounds(dev):
+    """The status tests above run one agent at a time; here the exits of vk_polymerize.h's loop are
+    taken per lane under the wave-wide __any, beside neighbours that go on.  Two steps, every array
+    bitwise against the restatement, columns >= n included."""
+    from lens_amd import native
+    model, sm, (lists, molecules, counts, keys), want, worst = ragged_wave_case()
+    n = len(lists)
+    assert worst >= tref.MARGIN                                          # no agent is left out
+    first, last = want[0], want[-1]
+    assert [a for a in range(n) if last[4][a] & native.VK_TL_BAD_KEY] == [3, 40]
+    assert first[4][7] & native.VK_TL_SLOTS_FULL and len(first[0][7]) == CAP
+    stopped = (first[4] & native.VK_TL_MAX_EVENTS) != 0
+    assert np.all(first[3][stopped] == 2) and 0 < stopped[:64].sum() < 64 and first[3][:64].min() == 0
+    assert len({int(e) for e in first[3][:64]}) == 3                    # lanes that fired 0, 1 and 2 times
+    got = _run(dev, model, sm, lists, molecules, counts, keys, n, 1.0, 2, max_events=2)
+    _compare(got, want, n)
