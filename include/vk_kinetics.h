@@ -38,7 +38,7 @@
  *   vk_motility_step, vk_flagella_step, vk_contact_step, vk_contact_step_channels, vk_population_plan,
  *   vk_flagella_counts, vk_divide_flagella, vk_ssa_step, vk_ssa_propensities, vk_divide_counts,
  *   vk_ssa_flagella_target, vk_colony_metrics, vk_translation_step, vk_divide_ribosomes,
- *   vk_transcription_step, vk_rna_degradation_step
+ *   vk_transcription_step, vk_rna_degradation_step, vk_cell_step_tree
  *       are introduced by the comment blocks above their declarations.
  *
  * Conventions
@@ -456,7 +456,9 @@ enum vk_cell_row {
 
 enum vk_growth_model {
     VK_GROWTH_PROTEIN = 0,  /* GrowthProtein + TreeMass; divide when protein >= divide_protein */
-    VK_GROWTH_MASS = 1      /* Growth (mass*factor); DivisionVolume: divide when volume >= division_volume */
+    VK_GROWTH_MASS = 1,     /* Growth (mass*factor); DivisionVolume: divide when volume >= division_volume */
+    VK_GROWTH_TREE = 2      /* vk_cell_step_tree only: no growth process; mass = initial_mass + the weighted
+                               rows of the count table; DivisionVolume                                  */
 };
 
 enum vk_rng {
@@ -499,6 +501,55 @@ int vk_cell_step(const vk_cell_params *p, int64_t n_agents, int64_t ld, double *
                  double *mmol_to_counts, const double *u, const int32_t *root,
                  const int32_t *depth, const uint64_t *path, int32_t *divide,
                  vk_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * vk_cell_step_tree: vk_cell_step with TreeMass over a count table
+ *
+ * Stands where the reference runs TreeMass (tree_mass.py:10-18, 55-64) over a compartment
+ * whose Translation and Complexation ports hang an `mw` property on their proteins, complexes
+ * and transcripts (translation.py:347-400, complexation.py:84-97): mass = initial_mass + the
+ * sum over every node with `mw` of mw * (count / N_A), then DeriveGlobals on it.
+ *
+ * counts: the colony's int32 table [n_rows][ld_counts].  rows / weights: DEVICE arrays of
+ * n_weighted entries (0 <= n_weighted <= VK_TREE_MAX_WEIGHTED), rows strictly ascending in
+ * [0, n_rows), weights in g/mol.  initial_mass: [ld] fg, VK_GROWTH_TREE only.
+ *
+ * Per agent a, FP64 without contraction:
+ *   VK_GROWTH_PROTEIN  growth, the draw, the divide flag and the new protein pn exactly as in
+ *                      vk_cell_step; m = 0.0 + (protein_mw * (pn / avogadro)) * fg_per_g.
+ *   VK_GROWTH_TREE     div = (step-start volume >= division_volume); m = initial_mass[a]; the
+ *                      protein row is not touched.
+ *   both               for k = 0 .. n_weighted - 1 in that order:
+ *                        m = m + (weights[k] * ((double) counts[rows[k] * ld_counts + a] / avogadro)) * fg_per_g
+ *                      then vk_cell_step's deriver tail on m (mass, volume, mmol_to_counts,
+ *                      length, surface area) and divide[a] = div.
+ *   VK_GROWTH_MASS     is refused (VK_ERR_ARG): Growth writes the mass itself.
+ * With n_weighted == 0 and VK_GROWTH_PROTEIN the output is vk_cell_step's bit for bit.
+ *
+ * The per-node expression is calculate_mass with the g -> fg factor where pint applies it (the
+ * protein node of vk_cell_step, pinned by the colony_metrics fixture).  THE ENGINE'S OWN: the
+ * ORDER of the fold -- the aggregate protein first, then the table rows ascending.  The
+ * reference folds in its Store's depth-first dict order, which is not reproduced (pint and the
+ * reference's core do not import here); FP64 addition does not commute bit for bit, so the
+ * last bits of a mass may differ from the reference's.  UNVERIFIED against the reference for
+ * the same reason: pint's conversion bits for the table's nodes.
+ *
+ * Bad arguments return VK_ERR_ARG and launch nothing: a null pointer the model needs, n_weighted
+ * outside 0..VK_TREE_MAX_WEIGHTED or above n_rows, ld < n, ld_counts < n, VK_GROWTH_MASS or an
+ * unknown model or rng.  rows[] lives on the device and no call reads it back: the HOST SIDE
+ * validates it once, when it uploads it (lens_amd.cells.TreeWeights refuses a row out of range
+ * or not strictly ascending before anything is launched).  The C function trusts that; the
+ * kernel still reads nothing outside the table (a row outside [0, n_rows) counts as 0).
+ * One agent per lane, 256 lanes per workgroup; no LDS, no scratch, no atomics, no host read.
+ * ------------------------------------------------------------------------- */
+#define VK_TREE_MAX_WEIGHTED 256
+
+int vk_cell_step_tree(const vk_cell_params *p, int64_t n_agents, int64_t ld, double *cell,
+                      double *mmol_to_counts, const double *u, const int32_t *root,
+                      const int32_t *depth, const uint64_t *path, int32_t *divide,
+                      const int32_t *counts, int64_t ld_counts, int32_t n_rows,
+                      const int32_t *rows, const double *weights, int32_t n_weighted,
+                      const double *initial_mass, vk_stream_t stream);
 
 /* Division plan: src_index[j] = source agent of new slot j, kind[j] = -1 for a
  * survivor, 0 / 1 for daughter 0 / 1 (j < n_agents + n_divide).  n_out: one

@@ -124,7 +124,7 @@ import numpy as np
 import torch
 
 from lens_amd import native
-from lens_amd.cells import CellModel, lineage_ids
+from lens_amd.cells import CellModel, cell_step_tree, lineage_ids
 from lens_amd.colonies import ColonyShape, ColonyShapeModel
 from lens_amd.configs import initial_conc
 from lens_amd.degradation import DegradationEngine, DegradationModel, describe_status as describe_deg_status
@@ -193,6 +193,7 @@ class Colony:
     # Colony(stochastic=..., translation=..., transcription=..., degradation=...): what the table of
     # stages does not name; the engines, lists and pools it names are declared below the class
     stochastic = ssa = ssa_key = degradation = deg_partial = None
+    _tree = initial_mass = None                  # CellModel(molecular_weights=...) / model='tree_mass'
     _x_stream = _p_stream = None                 # capture(overlap=True)
     _counts_alt = flux_steps = counts_steps = nsteps_steps = None    # capture(overlap=True), step_many
     _colony_shape = None                         # colony_metrics
@@ -286,6 +287,13 @@ class Colony:
                                  'transcription=TranscriptionModel(...): its transcripts and enzymes are rows of that '
                                  'table, and the nucleotide pools are transcription\'s')
             degradation.bind(stochastic, transcription)      # ValueError: the table lacks a species
+        tree = None
+        if cells is not None and cells.weighted:
+            # checked before anything is built: TreeMass folds rows of the stochastic table
+            if stochastic is None:
+                raise ValueError('a CellModel with molecular_weights needs a colony with '
+                                 'stochastic=StochasticModel(...): the weighted rows are rows of that table')
+            tree = cells.bind(stochastic)        # ValueError: a name that is no row of the table
         if mechanics is not None:
             # checked before anything is built, like motility: the contact launch moves and
             # re-bins the agents on the device, on one whole plane
@@ -420,7 +428,15 @@ class Colony:
             volume_fl = CellModel(initial_mass=mass_fg).derive(mass_fg)[0]
             self._resp = ResponseEngine(self._resp_layout, dev, avogadro, volume_fl, t.n_reactions, t.n_ext)
         if cells is not None:
-            rows, m2c = cells.initial_rows(ld)
+            if tree is not None:
+                # TreeMass over the count table: the weighted rows (ascending) and their weights,
+                # uploaded once; the initial deriver pass folds the initial counts
+                self._tree = tree.upload(dev)
+                rows, m2c = cells.initial_rows(ld, weighted=tree.pairs(stochastic.initial))
+                if cells.model == 'tree_mass':
+                    self.initial_mass = torch.full((ld,), float(cells.initial_mass), dtype=torch.float64, device=dev)
+            else:
+                rows, m2c = cells.initial_rows(ld)
             self.cell = torch.from_numpy(rows).to(dev).contiguous()
             self.m2c.copy_(torch.from_numpy(m2c))
             self.divide = z(ld, dtype=torch.int32)
@@ -1528,9 +1544,17 @@ class Colony:
 
     def set_cell_mass(self, mass):
         """Per-agent masses (fg) for agents 0..n-1 with their derived volume,
-        length, surface area and mmol_to_counts (DeriveGlobals on each)."""
+        length, surface area and mmol_to_counts (DeriveGlobals on each).  In the
+        ``'tree_mass'`` model the values are the agents' ``initial_mass``: the mass row is
+        TreeMass of them over the current counts, by the host's fold."""
         cm = self.cells
         mass = np.ascontiguousarray(mass, dtype=np.float64)[:self.n]
+        if cm.model == 'tree_mass':
+            if mass.shape != (self.n,):
+                raise ValueError('set_cell_mass: one initial mass per agent')
+            self.initial_mass[:self.n].copy_(torch.from_numpy(mass))
+            counts = self.ssa[:, :self.n].cpu().numpy()
+            mass = np.ascontiguousarray(cm.tree_mass(None, self._tree.pairs(counts), mass))     # elementwise
         vol, m2c, length, area = cm.derive(mass)          # numpy: the same IEEE ops elementwise
         rows = self.cell[:, :self.n].cpu().numpy()
         rows[native.VK_CELL_MASS], rows[native.VK_CELL_VOLUME] = mass, vol
@@ -1553,10 +1577,17 @@ class Colony:
             if self.response is not None:
                 # an agent frozen before this step neither grows nor raises its division flag
                 self._resp.cells(False, n, self.frozen, self.cell, self.m2c, self.divide, self._resp_buf)
-            native.check(native._lib.vk_cell_step(
-                ctypes.byref(p), n, self.ld, native.ptr(self.cell), native.ptr(self.m2c), native.ptr(u),
-                native.ptr(self.lin_root), native.ptr(self.lin_depth), native.ptr(self.lin_path),
-                native.ptr(self.divide), native.stream_handle()), 'vk_cell_step')
+            if self._tree is not None:
+                # TreeMass folds the weighted rows of the counts this step left (the network,
+                # translation, transcription and degradation above have run)
+                native.check(cell_step_tree(p, n, self.ld, self.cell, self.m2c, u, self.lin_root, self.lin_depth,
+                                            self.lin_path, self.divide, self.ssa, self._tree, self.initial_mass),
+                             'vk_cell_step_tree')
+            else:
+                native.check(native._lib.vk_cell_step(
+                    ctypes.byref(p), n, self.ld, native.ptr(self.cell), native.ptr(self.m2c), native.ptr(u),
+                    native.ptr(self.lin_root), native.ptr(self.lin_depth), native.ptr(self.lin_path),
+                    native.ptr(self.divide), native.stream_handle()), 'vk_cell_step')
             if self.response is not None:
                 self._resp.cells(True, n, self.frozen, self.cell, self.m2c, self.divide, self._resp_buf)
         # the mother machine: the agents the contact launch flagged leave with this plan, and a

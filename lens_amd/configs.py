@@ -511,7 +511,12 @@ def flagella_degradation(data, transcription):
     return _degradation_model(data, transcription, set(transcription.product_sequences()))
 
 
-def flagella_gene_expression(tx_data, tl_data, cx_data, deg_data, operons=None, seed=SEED, **kw):
+# the rows whose '_divider' the reference's flagella agent overrides to 'set'
+# (flagella_schema_override, vivarium/compartments/flagella_expression.py:73-90)
+FLAGELLA_SET_DIVIDERS = ('CpxR', 'CRP', 'Fnr', 'endoRNAse')
+
+
+def flagella_gene_expression(tx_data, tl_data, cx_data, deg_data, operons=None, seed=SEED, set_dividers=False, **kw):
     """The four expression processes of the reference's flagella agent (``GeneExpression`` as
     flagella_expression.py:93-137 configures it: Transcription, Translation, RnaDegradation,
     Complexation) as what a Colony takes: ``{'stochastic', 'transcription', 'translation',
@@ -530,7 +535,9 @@ def flagella_gene_expression(tx_data, tl_data, cx_data, deg_data, operons=None, 
     transcripts; ``None`` is the whole chromosome.  ``max_rnaps``, ``sequence`` and
     ``sequence_path`` go to the TranscriptionModel, ``max_ribosomes``, ``sequences`` and
     ``release`` to the TranslationModel, ``seed`` to all three, anything else to the
-    StochasticModel."""
+    StochasticModel.  ``set_dividers=True`` applies the reference's schema override
+    (:data:`FLAGELLA_SET_DIVIDERS`): both daughters keep the mother's regulators and RNase; the
+    default splits every row, as before."""
     from lens_amd.stochastic import StochasticModel
     tx_kw = {k: kw.pop(k) for k in ('max_rnaps', 'sequence', 'sequence_path') if k in kw}
     tl_kw = {k: kw.pop(k) for k in ('max_ribosomes', 'sequences', 'release') if k in kw}
@@ -551,10 +558,79 @@ def flagella_gene_expression(tx_data, tl_data, cx_data, deg_data, operons=None, 
     initial.update({transcription.transcript_species.get(o, o): count
                     for o, count in deg_data['initial_state']['transcripts'].items()
                     if transcription.transcript_species.get(o, o) in passive})
+    if set_dividers:
+        kw['dividers'] = dict(kw.get('dividers') or {}, **{
+            name: 'set' for name in FLAGELLA_SET_DIVIDERS if name in species or name in passive})
     stochastic = StochasticModel(species, cx_data['stoichiometry'], cx_data['rates'], initial=initial, seed=seed,
                                  passive=passive, **kw)
     return {'stochastic': stochastic, 'transcription': transcription, 'translation': translation,
             'degradation': degradation}
+
+
+def flagella_molecular_weights(tl_data, transcription=None, complexes=None):
+    """The ``mw`` properties the reference hangs on the flagella agent's stores, as
+    ``{row name: g/mol}`` for ``CellModel(molecular_weights=...)``: ``tl_data['molecular_weight']``
+    (tests/golden/flagella_translation.json: vivarium/data/molecular_weight.py for every
+    translated protein) restricted to the names that will be rows of the count table, the
+    products of ``tl_data['transcripts']``; ``complexes`` ({name: g/mol}, the same file's entries
+    for the complexes: tests/golden/flagella_complex_weights.json) joins them as it is.
+    The translation fixture holds the proteins' weights only, so WITHOUT ``complexes`` the
+    heaviest nodes of the reference's cell -- ``flagella``, the motor, the motor switch, the
+    export apparatus, ``flhDC`` and its transcript -- weigh nothing: pass that fixture's dict
+    for the reference's cell.
+
+    With a ``transcription`` model also the transcripts: the reference looks the OPERON's name up
+    in the same dict (translation.py:389-393), so ``fliL``'s transcript weighs what the FliL
+    protein weighs and ``flhDC``'s what the complex weighs -- a name collision in the reference,
+    kept here, under the engine's ``<operon>_RNA`` row names.  An operon that names no protein or
+    complex has no weight, as there."""
+    weights = tl_data['molecular_weight']
+    out = {p: float(weights[p]) for _, p in map(tuple, tl_data['transcripts']) if p in weights}
+    out.update({str(name): float(w) for name, w in (complexes or {}).items()})
+    if transcription is not None:
+        named = dict({k: float(v) for k, v in weights.items()}, **out)
+        for operon, species in transcription.transcript_species.items():
+            if operon in named:
+                out[species] = named[operon]
+    return out
+
+
+def gene_expression_cell(tl_data, transcription=None, complexes=None, **cell):
+    """``GeneExpression``'s own cell (vivarium/compartments/gene_expression.py:62-77) as a
+    :class:`~lens_amd.cells.CellModel`: no growth process, TreeMass from 1339 fg over
+    :func:`flagella_molecular_weights`, DeriveGlobals, DivisionVolume.  It is the reference's
+    cell only with ``complexes`` (see there).  Further keyword arguments
+    (``division_volume``, ...) go to the CellModel."""
+    from lens_amd.cells import CellModel
+    cell.setdefault('initial_mass', 1339.0)
+    return CellModel(model='tree_mass', molecular_weights=flagella_molecular_weights(tl_data, transcription, complexes),
+                     **cell)
+
+
+def chemotaxis_expression_flagella(tx, tl, cx, deg, division='merged', complexes=None, expression=None, **motility):
+    """The reference's ChemotaxisExpressionFlagella compartment (vivarium/compartments/
+    chemotaxis_flagella.py:176-260) as what a Colony takes, in the manner of
+    :func:`chemotaxis_ode_expression_flagella`: the four expression models of
+    :func:`flagella_gene_expression` on the fixtures ``tx``, ``tl``, ``cx``, ``deg`` with the
+    reference's ``set`` dividers; ``cells``: GrowthProtein at growth rate 0.000275 from 1339 fg
+    with TreeMass from its default 0 fg over the aggregate protein and then the table
+    (:func:`flagella_molecular_weights`; ``complexes`` as there: without it the complexes weigh
+    nothing); ``motility``: the receptor
+    cluster at ligand ``MeAsp``, initial ligand 0.1 mM, and FlagellaActivity starting without
+    flagella, their count the ``flagella`` complex's.  ``expression``: keyword arguments of
+    :func:`flagella_gene_expression` (``operons``, ``seed``, ``max_rnaps``, ...); further
+    keyword arguments (``substeps``, ``seed``, ...) go to the MotilityModel."""
+    from lens_amd.cells import CellModel
+    from lens_amd.motility import FlagellaModel, MotilityModel
+    models = flagella_gene_expression(tx, tl, cx, deg, set_dividers=True, **(expression or {}))
+    weights = flagella_molecular_weights(tl, models['transcription'], complexes)
+    rows = set(models['stochastic'].rows)
+    motility.setdefault('ligand_id', 'MeAsp')
+    motility.setdefault('initial_ligand', 0.1)
+    models['cells'] = CellModel('growth_protein', growth_rate=0.000275, initial_mass=1339.0,
+                                molecular_weights={k: w for k, w in weights.items() if k in rows})
+    models['motility'] = MotilityModel(flagella=FlagellaModel(0, complexes='flagella'), division=division, **motility)
+    return models
 
 
 def deepcopy_config(cfg):

@@ -32,46 +32,59 @@
 // growth process + derivers
 // ---------------------------------------------------------------------------
 
+// The deriver tail of both cell kernels: the mass row, then globals_deriver on it
+// (derive_globals.py:131-152): volume = mass / density (magnitude), then .to('fL');
+// mmol_to_counts, length and surface area from the same magnitude.
+__device__ __forceinline__ void cell_derive(const vk_cell_params &p, double m, int64_t a, int64_t ld,
+                                            double *__restrict__ cell, double *__restrict__ m2c) {
+    cell[(int64_t)VK_CELL_MASS * ld + a] = m;
+    const double raw = m / p.density;
+    cell[(int64_t)VK_CELL_VOLUME * ld + a] = raw * p.volume_to_fl;
+    m2c[a] = p.avogadro * (raw * 1e-15) * 1e-3;
+    const double len = (raw - p.cap_volume) / p.cap_area + p.two_r;
+    cell[(int64_t)VK_CELL_LENGTH * ld + a] = len;
+    cell[(int64_t)VK_CELL_SURFACE_AREA * ld + a] = p.sa_const + p.sa_lin * (len - p.width);
+}
+
+// GrowthProtein.next_update from the step-start protein (growth_protein.py:88-107): writes the
+// new protein, returns it; div: the step-start protein reached divide_protein
+__device__ __forceinline__ double cell_grow_protein(const vk_cell_params &p, int64_t a, double *__restrict__ protein,
+                                                    const double *__restrict__ u, const int32_t *__restrict__ root,
+                                                    const int32_t *__restrict__ depth,
+                                                    const uint64_t *__restrict__ path, int32_t &div) {
+    const double pr = *protein;
+    const double total = pr * p.factor;
+    double added = trunc(total - pr);            // int(total - protein)
+    const double extra = total - trunc(total);   // total - int(total)
+    const double draw = (p.rng == VK_RNG_PHILOX)
+                            ? philox_uniform(p.seed, p.step, root[a], depth[a], path[a])
+                            : u[a];
+    if (draw < extra) added = added + 1.0;
+    div = pr >= p.divide_protein;
+    const double pn = pr + added;
+    *protein = pn;
+    return pn;
+}
+
 __global__ __launch_bounds__(256) void k_cell_step(vk_cell_params p, int64_t n, int64_t ld, double *__restrict__ cell,
                                                    double *__restrict__ m2c, const double *__restrict__ u,
                                                    const int32_t *__restrict__ root, const int32_t *__restrict__ depth,
                                                    const uint64_t *__restrict__ path, int32_t *__restrict__ divide) {
     const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= n) return;
-    double *mass = cell + (int64_t)VK_CELL_MASS * ld + a;
-    double *volume = cell + (int64_t)VK_CELL_VOLUME * ld + a;
-    double *length = cell + (int64_t)VK_CELL_LENGTH * ld + a;
-    double *area = cell + (int64_t)VK_CELL_SURFACE_AREA * ld + a;
-    double *protein = cell + (int64_t)VK_CELL_PROTEIN * ld + a;
+    const double *mass = cell + (int64_t)VK_CELL_MASS * ld + a;
+    const double *volume = cell + (int64_t)VK_CELL_VOLUME * ld + a;
     int32_t div;
     double m;
     if (p.model == VK_GROWTH_PROTEIN) {
-        // process, from the step-start protein
-        const double pr = *protein;
-        const double total = pr * p.factor;
-        double added = trunc(total - pr);            // int(total - protein)
-        const double extra = total - trunc(total);   // total - int(total)
-        const double draw = (p.rng == VK_RNG_PHILOX)
-                                ? philox_uniform(p.seed, p.step, root[a], depth[a], path[a])
-                                : u[a];
-        if (draw < extra) added = added + 1.0;
-        div = pr >= p.divide_protein;
-        const double pn = pr + added;
-        *protein = pn;
+        const double pn = cell_grow_protein(p, a, cell + (int64_t)VK_CELL_PROTEIN * ld + a, u, root, depth, path, div);
         // mass_deriver: 0 fg + mw * (count / N_A), g -> fg
         m = 0.0 + (p.protein_mw * (pn / p.avogadro)) * p.fg_per_g;
     } else {
         div = *volume >= p.division_volume;          // DivisionVolume, step-start volume
         m = *mass * p.factor;                         // Growth
     }
-    *mass = m;
-    // globals_deriver: volume = mass / density (magnitude), then .to('fL')
-    const double raw = m / p.density;
-    *volume = raw * p.volume_to_fl;
-    m2c[a] = p.avogadro * (raw * 1e-15) * 1e-3;
-    const double len = (raw - p.cap_volume) / p.cap_area + p.two_r;
-    *length = len;
-    *area = p.sa_const + p.sa_lin * (len - p.width);
+    cell_derive(p, m, a, ld, cell, m2c);
     divide[a] = div;
 }
 
@@ -104,6 +117,106 @@ extern "C" int vk_cell_step(const vk_cell_params *p, int64_t n, int64_t ld, doub
     hipLaunchKernelGGL(k_cell_step, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *p, n,
                        ld, cell, m2c, u, root, depth, path, divide);
     return vk::launch_check("k_cell_step");
+}
+
+// ---------------------------------------------------------------------------
+// TreeMass over the colony's count table (tree_mass.py:10-18, 55-64)
+// ---------------------------------------------------------------------------
+//
+// k_cell_step_tree is k_cell_step with the mass folded over weighted rows of the int32 count
+// table: m = m + (mw * (count / N_A)) * fg_per_g per weighted row, rows ascending, after the
+// aggregate protein (VK_GROWTH_PROTEIN) or from initial_mass[a] (VK_GROWTH_TREE).  The per-node
+// expression is calculate_mass with pint's g -> fg factor; the ORDER of the fold is THE ENGINE'S
+// OWN (the reference folds in its Store's depth-first dict order; include/vk_kinetics.h).
+//
+// Layout.  One agent per lane.  rows[] and weights[] are the same for every lane: wave-uniform
+// addresses (ldc: the scalar cache).  A count is row * ld_counts + a: a wave's loads coalesce.
+// The rows go in chunks of TREE_CHUNK whose loads are all issued before the chunk's arithmetic,
+// so a lane has TREE_CHUNK loads in flight, not one dependent load after another.  The division
+// by avogadro stays a division (a reciprocal multiply changes bits).  No LDS, no atomics.
+// A row outside [0, n_rows) reads nothing and counts 0: the host side validates rows[]
+// (lens_amd.cells.TreeWeights), the guard only keeps an unvalidated caller inside the table.
+
+#define TREE_CHUNK 16
+
+__global__ __launch_bounds__(256) void k_cell_step_tree(
+    vk_cell_params p, int64_t n, int64_t ld, double *__restrict__ cell, double *__restrict__ m2c,
+    const double *__restrict__ u, const int32_t *__restrict__ root, const int32_t *__restrict__ depth,
+    const uint64_t *__restrict__ path, int32_t *__restrict__ divide, const int32_t *__restrict__ counts,
+    int64_t ld_counts, int32_t n_rows, const int32_t *__restrict__ rows, const double *__restrict__ weights,
+    int32_t n_weighted, const double *__restrict__ initial_mass) {
+    const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= n) return;
+    int32_t div;
+    double m;
+    if (p.model == VK_GROWTH_PROTEIN) {
+        const double pn = cell_grow_protein(p, a, cell + (int64_t)VK_CELL_PROTEIN * ld + a, u, root, depth, path, div);
+        m = 0.0 + (p.protein_mw * (pn / p.avogadro)) * p.fg_per_g;
+    } else {
+        div = cell[(int64_t)VK_CELL_VOLUME * ld + a] >= p.division_volume;   // DivisionVolume, step-start volume
+        m = initial_mass[a];
+    }
+    for (int k0 = 0; k0 < n_weighted; k0 += TREE_CHUNK) {
+        int32_t x[TREE_CHUNK];
+#pragma unroll
+        for (int i = 0; i < TREE_CHUNK; ++i) {
+            x[i] = 0;
+            if (k0 + i < n_weighted) {
+                const int row = ldc(rows, k0 + i);
+                if ((unsigned)row < (unsigned)n_rows) x[i] = counts[(int64_t)row * ld_counts + a];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < TREE_CHUNK; ++i)
+            if (k0 + i < n_weighted) m = m + (ldc(weights, k0 + i) * ((double)x[i] / p.avogadro)) * p.fg_per_g;
+    }
+    cell_derive(p, m, a, ld, cell, m2c);
+    divide[a] = div;
+}
+
+extern "C" int vk_cell_step_tree(const vk_cell_params *p, int64_t n, int64_t ld, double *cell, double *m2c,
+                                 const double *u, const int32_t *root, const int32_t *depth, const uint64_t *path,
+                                 int32_t *divide, const int32_t *counts, int64_t ld_counts, int32_t n_rows,
+                                 const int32_t *rows, const double *weights, int32_t n_weighted,
+                                 const double *initial_mass, vk_stream_t stream) {
+    if (!p || n < 0 || ld < n || ld_counts < n || n_rows < 0 || n_weighted < 0 || n_weighted > VK_TREE_MAX_WEIGHTED ||
+        n_weighted > n_rows || (n > 0 && (!cell || !m2c || !divide)) ||
+        (n > 0 && n_weighted > 0 && (!counts || !rows || !weights))) {
+        vk::set_error("vk_cell_step_tree: bad arguments (n <= ld, n <= ld_counts, 0 <= n_weighted <= %d and <= n_rows)",
+                      VK_TREE_MAX_WEIGHTED);
+        return VK_ERR_ARG;
+    }
+    if (p->model == VK_GROWTH_MASS) {
+        vk::set_error("vk_cell_step_tree: VK_GROWTH_MASS writes the mass itself (vk_cell_step)");
+        return VK_ERR_ARG;
+    }
+    if (p->model != VK_GROWTH_PROTEIN && p->model != VK_GROWTH_TREE) {
+        vk::set_error("vk_cell_step_tree: unknown growth model %d", p->model);
+        return VK_ERR_ARG;
+    }
+    if (p->model == VK_GROWTH_TREE && n > 0 && !initial_mass) {
+        vk::set_error("vk_cell_step_tree: VK_GROWTH_TREE needs initial_mass[]");
+        return VK_ERR_ARG;
+    }
+    if (p->model == VK_GROWTH_PROTEIN && n > 0) {
+        if (p->rng == VK_RNG_STREAM && !u) {
+            vk::set_error("vk_cell_step_tree: VK_RNG_STREAM needs u[]");
+            return VK_ERR_ARG;
+        }
+        if (p->rng == VK_RNG_PHILOX && (!root || !depth || !path)) {
+            vk::set_error("vk_cell_step_tree: VK_RNG_PHILOX needs the lineage arrays");
+            return VK_ERR_ARG;
+        }
+        if (p->rng != VK_RNG_STREAM && p->rng != VK_RNG_PHILOX) {
+            vk::set_error("vk_cell_step_tree: unknown rng %d", p->rng);
+            return VK_ERR_ARG;
+        }
+    }
+    if (n == 0) return VK_OK;
+    hipLaunchKernelGGL(k_cell_step_tree, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *p, n,
+                       ld, cell, m2c, u, root, depth, path, divide, counts, ld_counts, n_rows, rows, weights,
+                       n_weighted, initial_mass);
+    return vk::launch_check("k_cell_step_tree");
 }
 
 // ---------------------------------------------------------------------------

@@ -40,6 +40,7 @@ EXPORTS = (
     'vk_colonies_scratch_bytes', 'vk_colony_metrics',
     'vk_gradient_fill', 'vk_static_gather', 'vk_motility_step_static', 'vk_flagella_step_static',
     'vk_translation_step', 'vk_divide_ribosomes', 'vk_transcription_step', 'vk_rna_degradation_step',
+    'vk_cell_step_tree',
 )
 
 VK_CELL_MASS, VK_CELL_VOLUME, VK_CELL_LENGTH, VK_CELL_SURFACE_AREA, VK_CELL_PROTEIN, VK_CELL_ANGLE = range(6)
@@ -78,7 +79,8 @@ VK_COLONY_ROWS = 10
 VK_COLONIES_TOO_LONG, VK_COLONIES_GAVE_UP = 1, 2
 VK_GRADIENT_UNIFORM, VK_GRADIENT_GAUSSIAN, VK_GRADIENT_LINEAR, VK_GRADIENT_EXPONENTIAL = range(4)
 VK_GRADIENT_MAX = 8
-VK_GROWTH_PROTEIN, VK_GROWTH_MASS = 0, 1
+VK_GROWTH_PROTEIN, VK_GROWTH_MASS, VK_GROWTH_TREE = 0, 1, 2
+VK_TREE_MAX_WEIGHTED = 256
 VK_RNG_STREAM, VK_RNG_PHILOX = 0, 1
 VK_DIVIDE_SET, VK_DIVIDE_SPLIT, VK_DIVIDE_ZERO = 0, 1, 2
 VK_UNIFORM_BLOCKS = 512
@@ -245,6 +247,8 @@ _SIGS = {
     'vk_bin_sites': ([_vp, _i64, _i64, _i32, _i32, _f64, _f64, _i32, _vp, _vp, _vp], ctypes.c_int),
     'vk_cell_step': ([ctypes.POINTER(VkCellParams), _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
                      ctypes.c_int),
+    'vk_cell_step_tree': ([ctypes.POINTER(VkCellParams), _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                           _i32, _vp, _vp, _i32, _vp, _vp], ctypes.c_int),
     'vk_divide_scratch_bytes': ([_i64], ctypes.c_int64),
     'vk_divide_plan': ([_vp, _i64, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     'vk_divide_gather': ([_i64, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp], ctypes.c_int),

@@ -59,8 +59,10 @@ AGENT_ARRAYS = (
 # The per-agent arrays of Colony(stochastic=...), two more rows of the same table, reported
 # after the ones above: the int counts of the stochastic network, split by divide_split with
 # a coin per (mother, species), and the key each agent draws by; daughters get fresh keys
-# (vk_divide_counts)
-STOCHASTIC_ARRAYS = (('ssa', 'counts'), ('ssa_key', 'counts'))
+# (vk_divide_counts).  With them stands TreeMass's ``global.initial_mass`` ([ld] FP64, fg), which
+# only a colony whose CellModel is 'tree_mass' holds -- its mass is folded over these counts, so
+# it always has them: the reference's '_divider': 'split' (tree_mass.py:41-45)
+STOCHASTIC_ARRAYS = (('ssa', 'counts'), ('ssa_key', 'counts'), ('initial_mass', _SPLIT))
 # The per-agent arrays of Colony(translation=...): the ribosome list ([max_ribosomes][ld], one
 # packed word per ribosome, in insertion order) and its length, divided entry by entry with a
 # coin per (mother, entry) (vk_divide_ribosomes), and the monomers, ATP and ADP, split by

@@ -27,6 +27,7 @@ from lens_amd import native
 
 MAX_SPECIES, MAX_REACTIONS, MAX_ORDER = native.VK_SSA_MAX_SPECIES, native.VK_SSA_MAX_REACTIONS, native.VK_SSA_MAX_ORDER
 MAX_PASSIVE = 192                      # further rows of the count table that no reaction names
+DIVIDER_NAMES = ('set', 'split')       # what a count row may declare (StochasticModel(dividers=...))
 STATUS_NAMES = ((native.VK_SSA_MAX_EVENTS, 'max_events reached'), (native.VK_SSA_NONFINITE, 'propensity not finite'),
                 (native.VK_SSA_OVERFLOW, 'a count would pass 2**31 - 1'), (native.VK_SSA_BAD_KEY, 'key outside [0, 2**31)'))
 
@@ -60,15 +61,28 @@ class StochasticModel:
     ``passive``: ids of further rows of the count table, after the ``species`` rows, that no
     reaction may name (at most 192).  The network's launches stage and read the ``species`` rows
     only; translation, transcription and degradation may write any row (:attr:`rows`), and
-    division splits them all.  ``n_species`` and the packed arrays stay the network's own."""
+    division splits them all.  ``n_species`` and the packed arrays stay the network's own.
+
+    ``dividers``: ``{row: 'set' | 'split'}`` over any rows, active or passive (default
+    ``'split'``): both daughters of a mother keep her count of a ``'set'`` row, as the
+    reference's flagella agent keeps its regulators and its RNase ('_divider': 'set',
+    flagella_expression.py:73-90).  It changes nothing but division."""
 
     def __init__(self, species: Sequence[str], stoichiometry: Dict[str, Dict[str, int]], rates,
                  initial: Optional[Dict[str, int]] = None, seed: int = 0, max_events: int = 100000,
-                 passive: Sequence[str] = ()):
+                 passive: Sequence[str] = (), dividers: Optional[Dict[str, str]] = None):
         self.species = [str(s) for s in species]
         self.passive = [str(s) for s in passive]
         if len(set(self.species + self.passive)) != len(self.species) + len(self.passive):
             raise ValueError('stochastic: species ids must be distinct')
+        self.dividers = {}
+        for name, divider in (dividers or {}).items():
+            if name not in self.species and name not in self.passive:
+                raise ValueError('stochastic: dividers names the unknown row %r' % (name,))
+            if divider not in DIVIDER_NAMES:
+                raise ValueError('stochastic: the divider of %r must be one of %s (got %r)' % (
+                    name, sorted(DIVIDER_NAMES), divider))
+            self.dividers[str(name)] = divider
         S = len(self.species)
         if not 1 <= S <= MAX_SPECIES:
             raise ValueError('stochastic: 1..%d species (got %d)' % (MAX_SPECIES, S))
@@ -162,6 +176,17 @@ class StochasticModel:
         if species not in rows:
             raise ValueError('stochastic: no species %r (species: %s)' % (species, rows))
         return rows.index(species)
+
+    def set_runs(self):
+        """The maximal runs [lo, hi) of consecutive table rows whose divider is ``'set'``."""
+        runs = []
+        for r, name in enumerate(self.rows):
+            if self.dividers.get(name) == 'set':
+                if runs and runs[-1][1] == r:
+                    runs[-1][1] = r + 1
+                else:
+                    runs.append([r, r + 1])
+        return [tuple(run) for run in runs]
 
     def initial_counts(self, n: int, ld: int) -> np.ndarray:
         out = np.zeros((self.n_rows, ld), dtype=np.int32)
@@ -265,8 +290,9 @@ def passive_seed(seed, chunk):
 def divide_agent_counts(col, plan, old, new, ld):
     """The colony's divider of ``ssa`` / ``ssa_key`` (population.DIVIDERS): divide_split on every
     row, a coin per (mother, row) keyed by the mother's key; daughters get the keys from
-    the colony's base on.  Once installed: the base moves past them, and the daughters' motors
-    read their own share of the flagella complex."""
+    the colony's base on.  The rows the model declares ``'set'`` are then copied from the
+    mother.  Once installed: the base moves past them, and the daughters' motors read their
+    own share of the flagella complex."""
     base = col._ssa_key_base
     if base + plan.n_daughters - 1 > 2 ** 31 - 1:
         raise OverflowError('a stochastic key would pass 2**31 - 1 (the kernel puts it into a 32-bit counter word)')
@@ -279,6 +305,12 @@ def divide_agent_counts(col, plan, old, new, ld):
         hi = min(lo + MAX_SPECIES, rows)
         divide_counts(plan.n_out, plan.n_keep, plan.n_src, plan.src, plan.kind, old['ssa'][lo:hi], old['ssa_key'],
                       new['ssa'][lo:hi], new['ssa_key'], passive_seed(col.stochastic.seed, chunk), col.step_index, base)
+    # the 'set' rows: over what the split wrote, each run of them copied from the mother (no coin
+    # of any other row moves: the coins go by mother and row index within their launch)
+    for lo, hi in col.stochastic.set_runs():
+        native.check(native._lib.vk_divide_gather(
+            *plan.ptrs, native.ptr(old['ssa'][lo:hi]), old['ssa'].shape[-1], native.ptr(new['ssa'][lo:hi]),
+            new['ssa'].shape[-1], hi - lo, 4, native.VK_DIVIDE_SET, native.stream_handle()), 'vk_divide_gather(ssa set)')
 
     def installed(col):
         col._ssa_key_base = base + plan.n_daughters
